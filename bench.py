@@ -25,6 +25,11 @@ torch.distributed.run, before any GPU call) unless it already runs under a launc
 (WORLD_SIZE set, as the driver's torchrun). Rank 0 draws the global batch and broadcasts
 it (RCCL), every rank generates its shard (weak scaling, no per-step collective), ids are
 all-gathered. value = tokens of all ranks / max rank time.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step returned (``DIR/*.npy``, see
+``dump_outputs``). ``--full`` adds every other measurement to the line: the ``parity``
+sub-run, the ``roofline`` legs, ``fast_token_agreement`` and the ``cpu_baseline``.
 """
 from __future__ import annotations
 
@@ -83,6 +88,30 @@ def request_seed(step_i: int, gidx: int) -> int:
     return 1000 * step_i + gidx
 
 
+WAV_DUMP_ELEMS = 8 * 2 ** 20   # float32 waveform samples kept by --dump-outputs (32 MiB)
+
+
+def dump_outputs(path: str, gen, wav=None) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as float32 .npy files.
+    gen.npy [rows, longest row]: every request's generated audio token ids in request order
+    (all ranks' rows), short rows padded with -1; gen_lens.npy [rows]: the rows' lengths.
+    wav.npy (C5 only): rank 0's decoded waveforms [rows, 1, frames * hop], or, when they hold
+    more than WAV_DUMP_ELEMS samples, a fixed seeded sample of the flattened array (sorted
+    positions, the same for every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    ids = np.full((len(gen), max([1] + [len(g) for g in gen])), -1.0, dtype=np.float32)
+    for b, g in enumerate(gen):
+        ids[b, :len(g)] = np.asarray(g, dtype=np.float32)
+    np.save(os.path.join(path, "gen.npy"), ids)
+    np.save(os.path.join(path, "gen_lens.npy"), np.asarray([len(g) for g in gen], dtype=np.float32))
+    if wav is not None:
+        w = np.ascontiguousarray(wav, dtype=np.float32)
+        if w.size > WAV_DUMP_ELEMS:
+            keep = np.random.default_rng(20251226).choice(w.size, size=WAV_DUMP_ELEMS, replace=False)
+            w = w.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, "wav.npy"), w)
+
+
 def cpu_model() -> str:
     """The host CPU (model name of /proc/cpuinfo, and the logical CPUs the process may use)."""
     name = "unknown"
@@ -134,10 +163,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need and add it "
+                         "to the line: the `parity` sub-run, the `roofline` legs, `fast_token_agreement` and "
+                         "the `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32): gen, gen_lens, "
+                         "and wav on the C5 workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--parity-steps", type=int, default=1,
-                    help="timed generate() calls of the parity (drop-in default) path reported in the line's "
-                         "`parity` object (0: skip)")
+                    help="--full: timed generate() calls of the parity (drop-in default) path reported in the "
+                         "line's `parity` object (0: skip)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3",
                     help="BASELINE config: c2 / c3 (default) / c4 / c5 (= --e2e)")
     ap.add_argument("--parity", action="store_true",
@@ -164,6 +200,8 @@ def main():
                     help="nccl (= RCCL, default) or gloo (CPU collectives; lets N ranks share one GPU "
                          "to rehearse the sharded path)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.e2e:
         args.workload = "c5"
     wl_b, wl_tx, wl_tp, wl_e2e, wl_cfg = WORKLOADS[args.workload]
@@ -267,17 +305,21 @@ def main():
                 codes[b, :f.numel()] = f
             torch.cuda.synchronize(dev)
             t_c = time.perf_counter()
-            codec.decode(codes, lens=lens)
+            last["wav"] = codec.decode(codes, lens=lens)
             torch.cuda.synchronize(dev)
             codec_s[0] += time.perf_counter() - t_c
             audio_frames[0] += sum(lens)
         return [g.tolist() for g in out["gen"]]
 
+    last = {"gen": None, "wav": None}   # what the latest step returned (--dump-outputs)
+
     def step(i):
         if dist is None:
-            return sum(len(g) for g in generate(rows, i))
+            last["gen"] = generate(rows, i)
+            return sum(len(g) for g in last["gen"])
         before = gen_tokens[0]
-        run_sharded(rows, costs, lambda sh: generate(sh, i), comm_dev, max_per_rank=B, max_len=n_tok_row + 8)
+        last["gen"], _ = run_sharded(rows, costs, lambda sh: generate(sh, i), comm_dev, max_per_rank=B,
+                                     max_len=n_tok_row + 8)
         return gen_tokens[0] - before
 
     s_before = eng.attn_in_block_launches()
@@ -309,10 +351,13 @@ def main():
         tokens_all, frames_all, dt_max = float(tokens), float(audio_frames[0]), dt
     value = tokens_all / dt_max
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["gen"], None if last["wav"] is None else last["wav"].cpu().numpy())
+
     # ---- the drop-in default path (parity mode: token-exact to the reference) on the same
     # workload, timed after the headline region: one untimed warm-up, PARITY_STEPS timed
     parity_line = None
-    if world == 1 and not args.e2e and not args.parity and args.parity_steps > 0:
+    if args.full and world == 1 and not args.e2e and not args.parity and args.parity_steps > 0:
         saved = gen_tokens[0]
         generate(rows, 50, parity=True)   # warm-up: exact weight images, graphs
         torch.cuda.synchronize(dev)
@@ -371,7 +416,7 @@ def main():
     # ---- roofline of the dominant kernel: the fused decode-MLP launch (norm + gate/up +
     # down, 127 MB of weights per layer), or the gate/up GEMV when the MLP runs unfused
     roof = None
-    if rank == 0 and not args.e2e and not args.parity:
+    if args.full and rank == 0 and not args.e2e and not args.parity:
         import ctypes as C
         from t5gemma_tts_amd import _lib
         L = _lib.lib()
@@ -430,7 +475,7 @@ def main():
     # device time, profiles/r06_c5_kernel_stats.csv), every GEMM launch of whole B x 751-frame
     # decodes between its own HIP events on the launching stream; 2 M N K flops against the
     # f32 MFMA peak (157.3 TFLOP/s: v_mfma_f32_32x32x2_f32 runs at the f32 vector rate)
-    if rank == 0 and args.e2e:
+    if args.full and rank == 0 and args.e2e:
         import ctypes as C
         Tc = n_tok_row
         g = torch.Generator(device="cpu").manual_seed(7)
@@ -458,7 +503,7 @@ def main():
                 "decode_us": round(d_us.value, 1), "gemm_share_of_decode": round(g_us.value / d_us.value, 4)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.e2e:
         r0 = rows[0]
         cpu = cpu_baseline(cfg, sd, (r0[2:2 + r0[0]], r0[2 + r0[0]:], r0[1]), n_tok_row)
 
@@ -516,7 +561,7 @@ def main():
                 "attn_in_block_launches": int(s_launches),
                 "attn_in_block_mode": s_mode,   # 2 tail, 1 front (several passes past 3 slots / CU), 0 own launch
             }
-            if not args.parity:
+            if args.full and not args.parity:
                 # teacher-forced: the reference sampler on the reference CPU run's logits picks
                 # the fast path's token (full-depth report of this tree's fast-path sources)
                 from t5gemma_tts_amd import _lib

@@ -56,6 +56,49 @@ def test_cli_flags(monkeypatch):
         bench.main()
 
 
+def test_full_and_dump_outputs_flags(monkeypatch):
+    """--full is off by default; --full and --dump-outputs DIR reach main() (parse only)."""
+    import argparse
+    import sys
+    import bench
+    seen = []
+    orig = argparse.ArgumentParser.parse_args
+
+    def checking_parse(self, args=None, namespace=None):
+        seen.append(orig(self, args, namespace))
+        raise SystemExit(0)
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", checking_parse)
+    for argv in (["--gpus", "1", "--steps", "2", "--warmup", "1"],
+                 ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--dump-outputs", "some/dir"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.main()
+    assert not seen[0].full and seen[0].dump_outputs is None and seen[0].steps == 2
+    assert seen[1].full and seen[1].dump_outputs == "some/dir"
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 arrays: ragged token rows padded with -1 beside their
+    lengths, the waveform whole while small and as the same seeded sample once it is large."""
+    import numpy as np
+    import bench
+    d = str(tmp_path / "out")
+    wav = np.arange(2 * 1 * 12, dtype=np.float64).reshape(2, 1, 12)
+    bench.dump_outputs(d, [[5, 6, 7], [9]], wav)
+    gen, lens, w = (np.load(os.path.join(d, n + ".npy")) for n in ("gen", "gen_lens", "wav"))
+    assert gen.dtype == lens.dtype == w.dtype == np.float32
+    assert gen.tolist() == [[5, 6, 7], [9, -1, -1]] and lens.tolist() == [3, 1]
+    assert w.shape == (2, 1, 12) and (w == wav).all()
+    monkeypatch.setattr(bench, "WAV_DUMP_ELEMS", 7)
+    bench.dump_outputs(d, [[1]], wav)
+    s1 = np.load(os.path.join(d, "wav.npy"))
+    bench.dump_outputs(d, [[1]], wav + 100)
+    s2 = np.load(os.path.join(d, "wav.npy"))
+    assert s1.shape == (7,) and (np.diff(s1) > 0).all() and (s2 == s1 + 100).all()
+    bench.dump_outputs(d, [[1]])   # no codec: the token files only are rewritten
+    assert np.load(os.path.join(d, "gen.npy")).tolist() == [[1]]
+
+
 def test_cpu_baseline_tiny():
     """The CPU baseline times one whole utterance end to end on a tiny model (and reports its
     sample)."""
