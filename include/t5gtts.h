@@ -330,13 +330,24 @@ int t5g_engine_set_sampler_path(t5g_engine* e, int32_t single_block);
 /* Decode step layout (fast path; parity mode runs the exact-order kernels): each decoder
  * layer after its self attention -- o-projection, norm, cross-q, PM cross attention,
  * cross-o, norm, gate/up GeGLU, down, norm, the next layer's q|k|v -- as ONE persistent
- * launch with in-launch hand-offs (fused.hip; 1-16 rows; 17-32 rows fuse the MLP half) or as
- * per-op launches; bitwise equal. Default on. Computes the reference's PMDecoderLayer
+ * launch with in-launch hand-offs (fused.hip; 1-16 rows with one 16-row MFMA tile per stage;
+ * 17-32 rows with two tiles once t5g_engine_set_block_max_rows(e, 32) allows it, otherwise
+ * 17-32 rows fuse the MLP half) or as per-op launches; bitwise equal. Default on. Computes the reference's PMDecoderLayer
  * (hf_export/modeling_t5gemma_voice.py:256-323, [tf] modeling_t5gemma.py:81-97); no
  * reference-side equivalent switch. The switch also selects parity mode's persistent layer
  * (xlayer.hip: the same stages in the reference's CPU order, 1-8 decode rows of <= 64 text
  * keys each; bitwise equal to parity mode's per-op launches). */
 int t5g_engine_set_fused(t5g_engine* e, int32_t enable);
+/* The largest decode batch the whole-layer launch above takes: 16 (default; one 16-row MFMA
+ * tile per GEMV stage) or 32 (17-32 rows run the two-tile instantiations: a second tile in
+ * every GEMV stage, a norm workgroup per two rows, a cross-attention workgroup per (row, kv
+ * head) with its two q heads; stage S by the same slot rules as 1-16 rows). Any other value
+ * is T5G_EINVAL. Bitwise equal to the per-op launches at every batch size
+ * (tests/test_gpu_fused_rows32.py). No reference-side equivalent.
+ * t5g_engine_block_launches: whole-layer launches issued so far, with or without stage S (a
+ * launch captured into a graph counts once, at capture). */
+int t5g_engine_set_block_max_rows(t5g_engine* e, int32_t n);
+int t5g_engine_block_launches(t5g_engine* e, int64_t* n);
 /* Test / bench hook: parity-mode persistent layer launches issued so far (a launch captured
  * into a graph counts once, at capture). No reference-side equivalent. */
 int t5g_engine_xlayer_launches(t5g_engine* e, int64_t* n);

@@ -133,6 +133,8 @@ SIGNATURES = {
     "t5g_engine_set_exact": (C.c_int, [_P, _I, _P, _I]),
     "t5g_engine_set_sampler_path": (C.c_int, [_P, _I]),
     "t5g_engine_set_fused": (C.c_int, [_P, _I]),
+    "t5g_engine_set_block_max_rows": (C.c_int, [_P, _I]),
+    "t5g_engine_block_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_engine_xlayer_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_time_xlayer": (C.c_int, [_P, _I, _I, _P, C.POINTER(C.c_float)]),
     "t5g_engine_set_attn_in_block": (C.c_int, [_P, _I]),

@@ -92,6 +92,11 @@ struct t5g_engine {
     // the flash decode self-attention as stage S of the persistent layer launch (fast path,
     // t5g_engine_set_attn_in_block): no attention launch of its own between the layers
     int attn_in_block = 2;   // 0 own launch, 1 stage S in front of O1, 2 at the end of the previous launch
+    // the largest batch the whole-layer launch takes (t5g_engine_set_block_max_rows): 16 (one
+    // MFMA tile) or 32 (two tiles, fused_rows32.hip); larger batches run the per-op launches
+    // with the MLP-half launch
+    int block_max_rows = 16;
+    int64_t blk_launches = 0;   // whole-layer launches issued (t5g_engine_block_launches)
     int64_t s_launches = 0;   // persistent layer launches run with stage S (tests)
     int s_mode_used = 0;      // the last decode pass's stage-S placement: 2 tail, 1 front, 0 none
     float* afpart = nullptr;    // [B][Hkv][nsplit][G][D]
@@ -1288,7 +1293,7 @@ static int decoder_pass(t5g_engine* e, int M, const int* ids, const int* tok_row
     bool qkv_done = false;   // the previous layer's fused block projected this layer's q|k|v
     // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
     bool tail = false;
-    if (decode && e->attn_in_block == 2 && e->attn_flash && e->fused_mlp && M <= 16 && d == 2304 && f == 9216 &&
+    if (decode && e->attn_in_block == 2 && e->attn_flash && e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 &&
         s_o == 4 && s_down == 8 && s_qkv == 2 && e->q_dim == 2048 && c.n_dec_layers >= 2) {
         tail = true;
         for (int l = 0; l < c.n_dec_layers && tail; ++l) {
@@ -1348,17 +1353,19 @@ static int decoder_pass(t5g_engine* e, int M, const int* ids, const int* tok_row
                 FusedMlpArgs fa = fused_block_args(e, M, l);
                 if (!fused_block_tail(e, M, l, fa)) return T5G_EUNSUPPORTED;   // checked for every layer above
                 RC(fused_mlp(fa, st));
+                ++e->blk_launches;
                 if (l != c.n_dec_layers - 1) ++e->s_launches;
                 qkv_done = true;
                 continue;
             }
             // the persistent layer launch with the attention as its stage S (bitwise equal to
             // the flash launch below followed by the same launch without S)
-            if (e->fused_mlp && M <= 16 && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 && s_qkv == 2 &&
+            if (e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 && s_qkv == 2 &&
                 e->q_dim == 2048 && c.n_dec_layers >= 2) {
                 FusedMlpArgs fa = fused_block_args(e, M, l);
                 if (fused_mlp_check(fa) == 0 && fused_block_self(e, M, l, fa)) {
                     RC(fused_mlp(fa, st));
+                    ++e->blk_launches;
                     ++e->s_launches;
                     e->s_mode_used = 1;
                     qkv_done = l != c.n_dec_layers - 1;
@@ -1386,11 +1393,12 @@ static int decoder_pass(t5g_engine* e, int M, const int* ids, const int* tok_row
         // the rest of the layer (o-projection, cross attention, MLP half, the last norm and
         // the next layer's q|k|v) as one persistent launch (fused.hip fused_block_kernel;
         // bitwise equal to the launches below)
-        if (decode && e->fused_mlp && M <= 16 && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 &&
+        if (decode && e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 &&
             e->q_dim == 2048 && c.n_dec_layers >= 2) {
             const FusedMlpArgs fa = fused_block_args(e, M, l);
             if (fused_mlp_check(fa) == 0) {
                 RC(fused_mlp(fa, st));
+                ++e->blk_launches;
                 qkv_done = !last;
                 continue;
             }
@@ -1793,6 +1801,21 @@ extern "C" int t5g_engine_attn_in_block_launches(t5g_engine* e, int64_t* n) {
     return T5G_OK;
 }
 
+extern "C" int t5g_engine_block_launches(t5g_engine* e, int64_t* n) {
+    if (!e || !n) return T5G_EINVAL;
+    *n = e->blk_launches;
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_set_block_max_rows(t5g_engine* e, int32_t n) {
+    if (!e || (n != 16 && n != 32)) return T5G_EINVAL;
+    if (e->block_max_rows != n) {
+        e->block_max_rows = n;
+        drop_graphs(e);   // captured launches follow the limit
+    }
+    return T5G_OK;
+}
+
 extern "C" int t5g_engine_set_text_max(t5g_engine* e, int32_t n) {
     if (!e || n < 0 || n > e->c.max_text) return T5G_EINVAL;
     const int before = e->text_max > 0 ? e->text_max : e->c.max_text;
@@ -2139,6 +2162,8 @@ extern "C" int t5g_time_decode_layer(t5g_engine* e, int32_t B, int32_t iters, vo
     // attn_in_block 1: launch l runs layer l's attention in front; 2: layer l + 1's at its end
     // (the last launch none; layer 0's is the step's own launch, not timed here)
     // (mode 2 on a call the tail does not take runs S in front, as decoder_pass does)
+    // (the hook times the one-tile launch: past 16 rows bench.py prices the MLP-half launch)
+    if (B > 16) return T5G_EUNSUPPORTED;
     bool tail = e->attn_in_block == 2;
     FusedMlpArgs fa;
     for (int l = 0; l < L && tail; ++l) {

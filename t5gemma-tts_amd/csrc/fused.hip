@@ -33,7 +33,15 @@
 
 namespace t5g {
 
+// The two-tile (17-32 row) instantiations of fused_block_kernel are compiled as a translation
+// unit of their own (fused_rows32.hip includes this file with T5G_FUSED_ROWS32 defined):
+// instantiated beside the one-tile kernels they change the compiler's inlining decisions for
+// those, and the one-tile kernels stay the code they were.
+#ifdef T5G_FUSED_ROWS32
+T5G_TS_UNIT(fused_rows32)
+#else
 T5G_TS_UNIT(fused)
+#endif
 
 constexpr int FM_NW = 12;         // waves per workgroup (the gate/up and down kernels' count)
 constexpr int FM_NS = 4;          // cross-o split-K slabs read by the norm stage
@@ -416,35 +424,44 @@ __device__ __forceinline__ void fb_issue(bf16x8_s (&w)[UMAX][SPU], const bf16_t*
 // epilogue. OUT: 0 = GeGLU bf16 (sc1, 8 B), 1 = fp32 plain, 2 = fp32 sc1 (16 B).
 // LDSU: units i < nu_reg come from w, unit nu_reg (if < nu) from the LDS image lw (k-steps
 // 0 .. NWG * SPU - 1 of one unit, 1 KiB each, fragment layout) -- the same MFMAs in the
-// same order as from registers.
-template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false>
+// same order as from registers. MT: 16-row MFMA tiles (rows 16 t + lane % 16; every tile takes
+// the same weights through the same per-wave k-step chain, its partial sums in its own part of
+// `red`: unit i, tile t at (i MT + t) x NWG KiB).
+template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false, int MT = 1>
 __device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int gs, int nu, int kb_lo, int KBs,
                                           const bf16_t* X, int ldx, int xbytes, int M, void* Y, int ldy, int ybytes,
                                           int N, f32x4* red, const char* lw = nullptr, int nu_reg = 0) {
+    static_assert(MT == 1 || (!LDSU && EPI != EPI_GEGLU), "the LDS unit and the GeGLU epilogue are one-tile only");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int xr = lane & 15;
     wg_barrier();   // the hand-off is complete (or abandoned) for every wave past here
     if (wave < NWG) {
         const __amdgpu_buffer_rsrc_t xrs = raw_rsrc(X, (uint32_t)xbytes);
-        bf16x8_s xf[SPU];
         const bf16x8_s z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int xo = (min(xr, M - 1) * ldx + kb_lo * 32 + 8 * (lane >> 4)) * 2;
-#pragma unroll
-        for (int j = 0; j < SPU; ++j) {
-            const int kb = min(wave + j * NWG, KBs - 1);
-            const bf16x8_s v =
-                __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(xrs, xo + kb * 64, 0, AUX_SC1));
-            xf[j] = (xr < M && wave + j * NWG < KBs) ? v : z8;
-        }
         const int nr = LDSU ? nu_reg : nu;
+        // a tile at a time (its X fragments, then every unit's MFMAs): a stage that holds other
+        // requests in flight needs one tile's fragments in registers, not two
+        bf16x8_s xf[SPU];
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < MT; ++t) {
+            const int row = 16 * t + xr;
+            const int xo = (min(row, M - 1) * ldx + kb_lo * 32 + 8 * (lane >> 4)) * 2;
 #pragma unroll
-            for (int j = 0; j < SPU; ++j) acc = mfma16(w[i][j], xf[j], acc);
-            if (i < nr) red[(i * NWG + wave) * 64 + lane] = acc;
+            for (int j = 0; j < SPU; ++j) {
+                const int kb = min(wave + j * NWG, KBs - 1);
+                const bf16x8_s v =
+                    __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(xrs, xo + kb * 64, 0, AUX_SC1));
+                xf[j] = (row < M && wave + j * NWG < KBs) ? v : z8;
+            }
+#pragma unroll
+            for (int i = 0; i < UMAX; ++i) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < SPU; ++j) acc = mfma16(w[i][j], xf[j], acc);
+                if (i < nr) red[((i * MT + t) * NWG + wave) * 64 + lane] = acc;
+            }
         }
-        if constexpr (LDSU) {
+        if constexpr (LDSU) {   // (one tile)
             if (nu_reg < nu) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -457,38 +474,42 @@ __device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int 
     __syncthreads();
     constexpr bool GLU = EPI == EPI_GEGLU;
     const int n_out = GLU ? N / 2 : N;
-    const int m = xr;
-    if (wave >= NWG || m >= M || (GLU && lane >= 32)) return;
+    if (wave >= NWG || (MT == 1 && xr >= M) || (GLU && lane >= 32)) return;
     const __amdgpu_buffer_rsrc_t yr = raw_rsrc(Y, (uint32_t)ybytes);
-    for (int i = wave; i < nu; i += NWG) {
-        const f32x4* ri = red + (size_t)i * NWG * 64 + lane;
-        const int n0 = (g0 + i * gs) * (GLU ? 8 : 16) + 4 * (lane >> 4);
-        if constexpr (GLU) {
-            f32x4 gsum = {0.f, 0.f, 0.f, 0.f}, usum = gsum;
 #pragma unroll
-            for (int s2 = 0; s2 < NWG; ++s2) {
-                gsum += ri[s2 * 64];
-                usum += ri[s2 * 64 + 32];
-            }
-            float v[4];
+    for (int t = 0; t < MT; ++t) {
+        const int m = 16 * t + xr;
+        if (MT > 1 && m >= M) continue;
+        for (int i = wave; i < nu; i += NWG) {
+            const f32x4* ri = red + (size_t)(i * MT + t) * NWG * 64 + lane;
+            const int n0 = (g0 + i * gs) * (GLU ? 8 : 16) + 4 * (lane >> 4);
+            if constexpr (GLU) {
+                f32x4 gsum = {0.f, 0.f, 0.f, 0.f}, usum = gsum;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = rbf(gelu_tanh(rbf(gsum[r]))) * rbf(usum[r]);
-            const uint2 o2 = {pack2(v[0], v[1]), pack2(v[2], v[3])};
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o2), yr, (m * ldy + n0) * 2, 0, AUX_SC1);
-        } else {
-            f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
+                for (int s2 = 0; s2 < NWG; ++s2) {
+                    gsum += ri[s2 * 64];
+                    usum += ri[s2 * 64 + 32];
+                }
+                float v[4];
 #pragma unroll
-            for (int s2 = 0; s2 < NWG; ++s2) s4 += ri[s2 * 64];
-            if constexpr (OUT == 2) {
-                // n_out is a multiple of 16 here (the q / cross-o widths)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, s4), yr, (m * ldy + n0) * 4, 0,
-                                                       AUX_SC1);
+                for (int r = 0; r < 4; ++r) v[r] = rbf(gelu_tanh(rbf(gsum[r]))) * rbf(usum[r]);
+                const uint2 o2 = {pack2(v[0], v[1]), pack2(v[2], v[3])};
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o2), yr, (m * ldy + n0) * 2, 0, AUX_SC1);
             } else {
-                float* y = (float*)Y + (long)m * ldy;   // slabs read by the next launch
-                if (n0 + 3 < n_out) *(f32x4*)(y + n0) = s4;
-                else
-                    for (int r = 0; r < 4; ++r)
-                        if (n0 + r < n_out) y[n0 + r] = s4[r];
+                f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s2 = 0; s2 < NWG; ++s2) s4 += ri[s2 * 64];
+                if constexpr (OUT == 2) {
+                    // n_out is a multiple of 16 here (the q / cross-o widths)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, s4), yr, (m * ldy + n0) * 4, 0,
+                                                           AUX_SC1);
+                } else {
+                    float* y = (float*)Y + (long)m * ldy;   // slabs read by the next launch
+                    if (n0 + 3 < n_out) *(f32x4*)(y + n0) = s4;
+                    else
+                        for (int r = 0; r < 4; ++r)
+                            if (n0 + r < n_out) y[n0 + r] = s4[r];
+                }
             }
         }
     }
@@ -561,6 +582,10 @@ constexpr int FB_D = 2304;                                    // the block kerne
 constexpr int FB_GU_KB = FB_D / 32;                           // gate/up k-steps (= FM_NW x 6)
 constexpr size_t FB_GU_OFF = (5 * FM_NW * 1024 + sizeof(FbAttnLds) + 16 + 64 * sizeof(float) + FB_D * 2 + 1023) / 1024 * 1024;
 constexpr size_t FB_LDS = FB_GU_OFF + (size_t)FB_GU_KB * 1024;
+// two 16-row tiles (17-32 rows): the partial sums of both tiles (120 KB; gate/up's 5 units
+// stream through registers, no unit in LDS), one attention scratch per q head of the
+// workgroup's kv head, the norm scratch and a norm workgroup's two residual rows
+constexpr size_t FB_LDS2 = (2 * 5 * FM_NW * 1024 + 2 * sizeof(FbAttnLds) + 16 + 64 * sizeof(float) + 2 * FB_D * 2 + 1023) / 1024 * 1024;
 
 // ---- stage S: the layer's decode self-attention (a.self_attn), attn.hip
 // attn_decode_kernel<256, 2, true, true> + attn_flash_finish restated on this launch's 12
@@ -597,7 +622,7 @@ static_assert(sizeof(FbSelfLds) <= 5 * FM_NW * 1024, "stage S lives in the GEMV 
 // diagnostic timeline of stage S and O1 (T5G_DBG_TS library variant only,
 // tools/diag_fused_s.py): thread 0 (or `tid`) of every workgroup stores the 100 MHz clock at
 // numbered points, 32 slots per workgroup
-#ifdef T5G_DBG_TS
+#if defined(T5G_DBG_TS) && !defined(T5G_FUSED_ROWS32)
 __device__ unsigned long long* fs_ts_buf;
 extern "C" int t5g_dbg_set_fused_s(void* p) {
     return hipMemcpyToSymbol(HIP_SYMBOL(fs_ts_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
@@ -996,28 +1021,55 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
 // the next layer, followed by the next layer's O1 (a.self_tail; N1 then reads the previous
 // launch's o-projection slabs). Separate instantiations, so a launch carries only its own
 // stages' code and registers.
-template <int SM>
+//
+// MT: 16-row MFMA tiles. MT = 1 serves 1-16 rows, MT = 2 serves 17-32: every GEMV stage
+// multiplies each weight fragment into both tiles (fb_finish<.., MT>; gate/up streams its units double-buffered as fused_mlp_kernel<2> does,
+// fm_gemv<2>, because five resident units and two tiles of X do not fit 168 registers). The
+// worker maps change with it, the per-row arithmetic does not:
+//   norms       one workgroup per MT rows, one after the other ((M + 1) / 2 norm workgroups at
+//               MT = 2, so nw >= 240 workers and gate/up and down stay at <= 5 units each)
+//   attention   MT = 2: one workgroup per (row, kv head), its two q heads side by side on
+//               waves 0-3 and 4-7 (32 x 4 = 128 tasks; 32 x 8 (row, q head) tasks would
+//               outnumber the workers), each head with the one-head lane map and sums
+//   LDS         MT = 2: `red` holds both tiles (120 KB), no gate/up unit in LDS (FB_LDS2);
+//               the tail's stage S scratch lives in `red` (free between the q|k|v hand-off
+//               and the next layer's O1)
+//
+// One template parameter V = SM + 4 (MT - 1), so the one-tile kernels keep their names
+// (fused_block_kernel<0..2>; the profiles and tools/ name them) and their code.
+template <int V>
 __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a) {
+    constexpr int SM = V & 3, MT = 1 + (V >> 2);
+    static_assert(SM <= 2 && (MT == 1 || MT == 2), "S placement 0-2, one or two 16-row tiles");
     constexpr bool SELF = SM == 1;
+    constexpr int RED_B = 5 * MT * FM_NW * 1024;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    f32x4* red = (f32x4*)smem;                                   // GEMV partial sums, <= 60 KB
-    FbAttnLds& al = *(FbAttnLds*)(smem + 5 * FM_NW * 1024);      // attention scratch
-    float* nred = (float*)(smem + 5 * FM_NW * 1024 + sizeof(FbAttnLds) + 16);   // norm: 2 x 32 floats
-    // a norm workgroup's residual row between N1, N2 and N3 (bf16, exact: every h is rounded)
-    u32x4* hrow = (u32x4*)(smem + 5 * FM_NW * 1024 + sizeof(FbAttnLds) + 16 + 64 * sizeof(float));
+    f32x4* red = (f32x4*)smem;                                   // GEMV partial sums, <= 60 KB per tile
+    FbAttnLds* alv = (FbAttnLds*)(smem + RED_B);                 // attention scratch, one per head of the task
+    float* nred = (float*)(smem + RED_B + MT * sizeof(FbAttnLds) + 16);   // norm: 2 x 32 floats
+    // a norm workgroup's residual rows between N1, N2 and N3 (bf16, exact: every h is rounded)
+    u32x4* hrow = (u32x4*)(smem + RED_B + MT * sizeof(FbAttnLds) + 16 + 64 * sizeof(float));
     // a worker's last gate/up unit (72 KiB), fetched by LDS-DMA while the chain runs O1 -> O
+    // (one tile only)
     char* gul = smem + FB_GU_OFF;
     unsigned* tmo = a.timeout;
     const int bu = (int)blockIdx.x, nb = (int)gridDim.x;
     const int tq = (int)threadIdx.x, wave = tq >> 6, lane = tq & 63;
     const int d = a.d, f = a.f, M = a.M, D = 256;
+    FbAttnLds& al = alv[MT == 2 ? (wave >> 2) & 1 : 0];   // (two tiles: waves 0-3 and 4-7)
     T5G_TS(0);
     if (bu == 0 && tq < FM_SET_LINES)
         __hip_atomic_store(a.sync_next + tq * FM_LINE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int nn = (M + MT - 1) / MT;   // norm workgroups (MT rows each)
     const int nrow = bu - a.norm_b0;
-    const bool normwg = nrow >= 0 && nrow < M;
-    const bool attnwg = bu < M * a.Hq;
-    const int am = bu / a.Hq, ah = bu - am * a.Hq;   // attention task (row, q head)
+    const bool normwg = nrow >= 0 && nrow < nn;
+    // attention task: (row, q head), or at two tiles (row, kv head) with q head 2 kvh + wave / 4;
+    // aw / at: the wave / thread within its head's 4 waves
+    const int atasks = MT == 2 ? a.Hkv : a.Hq;
+    const bool attnwg = bu < M * atasks;
+    const int am = bu / atasks;
+    const int ah = MT == 2 ? 2 * (bu - am * atasks) + ((wave >> 2) & 1) : bu - am * atasks;
+    const int aw = MT == 2 ? wave & 3 : wave, at = MT == 2 ? tq & 255 : tq;
     bool ok = true;
     // ---- S: the layer's self-attention on every workgroup (O1 waits for its heads)
     if constexpr (SELF) {
@@ -1037,7 +1089,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     int len_tail = 0;
     if constexpr (SM == 2) {
         if (a.Wqkv) FS_TS(0);   // (the last layer's launch has no tail: its start would overwrite)
-        const int nwk = nb - M, cidx = bu + (wave >> 2) * nwk;
+        const int nwk = nb - nn, cidx = bu + (wave >> 2) * nwk;
         const int rk = cidx % (M * a.Hkv);
         len_tail = a.kv_len[bu < nwk ? rk / a.Hkv : 0];
     }
@@ -1050,7 +1102,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     float c8[8], s8[8];
     int alen = 0;
     auto kv_prefetch = [&]() __attribute__((always_inline)) {
-    if (attnwg && wave < 4) {
+    if (attnwg && wave < 4 * MT) {
         alen = a.enc_len[am];
         const int kvc = ah / (a.Hq / a.Hkv);
         const long hs = (long)a.kv_cap * D, bs = hs * a.Hkv;
@@ -1058,7 +1110,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         const __amdgpu_buffer_rsrc_t vrs = frag_rsrc(a.cv + am * bs + kvc * hs, (uint32_t)a.kv_cap * D * 2u);
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
-            const int j = i * KPB + wave * KPW + kg;
+            const int j = i * KPB + aw * KPW + kg;
             const int off = j < alen ? (j * D + 8 * dl) * 2 : (int)0x7ffffff0;
             kr[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, 0, 0));
             vr[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, off, 0, 0));
@@ -1076,45 +1128,101 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     }
     };
 
-    // ---- the norm workgroups (the last M): N1, N2, N3 for their row and nothing else, so no
+    // ---- the norm workgroups (the last nn): N1, N2, N3 for their rows and nothing else, so no
     // weight stream of their own ever queues ahead of a norm on the critical path
-    const int nw = nb - M;   // GEMV / attention workers
+    const int nw = nb - nn;   // GEMV / attention workers
     if (normwg) {
-        {
-            float hreg[8];
-            const int cc = min(tq, d / 8 - 1);
-            unpack8f(*(const u32x4*)(a.h + (long)nrow * d + 8 * cc), hreg);
-            if (a.Wo1) {   // the o-projection slabs come from this launch's O1 stage
-                if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_P0, (unsigned)(4 * (nw / 4)), tmo, 16u);
-                wg_barrier();
-                fb_norm<FM_NS, true>(a.o1slab, M, nrow, d, a.post1_w, a.pre1_w, a.eps, hreg, a.xn1, nred);
-            } else {
-                fb_norm<FM_NS, false>(a.o_slabs, M, nrow, d, a.post1_w, a.pre1_w, a.eps, hreg, a.xn1, nred);
+        if constexpr (MT == 1) {
+            {
+                float hreg[8];
+                const int cc = min(tq, d / 8 - 1);
+                unpack8f(*(const u32x4*)(a.h + (long)nrow * d + 8 * cc), hreg);
+                if (a.Wo1) {   // the o-projection slabs come from this launch's O1 stage
+                    if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_P0, (unsigned)(4 * (nw / 4)), tmo, 16u);
+                    wg_barrier();
+                    fb_norm<FM_NS, true>(a.o1slab, M, nrow, d, a.post1_w, a.pre1_w, a.eps, hreg, a.xn1, nred);
+                } else {
+                    fb_norm<FM_NS, false>(a.o_slabs, M, nrow, d, a.post1_w, a.pre1_w, a.eps, hreg, a.xn1, nred);
+                }
+                if (tq < d / 8) hrow[tq] = pack8f(hreg);
+                fb_publish(cline(a.sync, L_N1), 1u);
+                if constexpr (SELF) FS_TS(12);
             }
-            if (tq < d / 8) hrow[tq] = pack8f(hreg);
-            fb_publish(cline(a.sync, L_N1), 1u);
-            if constexpr (SELF) FS_TS(12);
+            {
+                if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_O0, (unsigned)(4 * (nw / 4)), tmo, 4u);
+                wg_barrier();
+                float r2[8];
+                unpack8f(hrow[min(tq, d / 8 - 1)], r2);
+                fb_norm<FM_NS, true>(a.oslab, M, nrow, d, a.post_w, a.pre_w, a.eps, r2, a.xn, nred);
+                if (tq < d / 8) hrow[tq] = pack8f(r2);
+                fb_publish(cline(a.sync, L_N2), 1u);
+            }
+            {
+                if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_D0, (unsigned)(FM_DS * (nw / FM_DS)), tmo, 14u);
+                wg_barrier();
+                float r3[8];
+                unpack8f(hrow[min(tq, d / 8 - 1)], r3);
+                fb_norm<FM_DS, true>(a.dslab, M, nrow, d, a.post3_w, a.pre3_w, a.eps, r3, a.xn, nred);
+                if (tq < d / 8) *(u32x4*)(a.h + (long)nrow * d + 8 * tq) = pack8f(r3);   // read by the next launch
+                fb_publish(cline(a.sync, L_N3), 1u);
+            }
+            T5G_TS(6);
+            return;
+        } else {
+            // two tiles: this workgroup's rows 2 nrow and 2 nrow + 1 (the last norm workgroup of
+            // an odd batch has one), one after the other through the same scratch, one arrival
+            // per row. (Its own branch: the one-tile code above stays as it was written.)
+            const int r0 = nrow * MT;
+            const int nr = min(MT, M - r0);   // rows here, workgroup-uniform
+            constexpr int HR = FB_D / 8;      // hrow words per row
+            {
+                float hreg[MT][8];
+                const int cc = min(tq, d / 8 - 1);
+#pragma unroll
+                for (int t = 0; t < MT; ++t) unpack8f(*(const u32x4*)(a.h + (long)min(r0 + t, M - 1) * d + 8 * cc), hreg[t]);
+                if (a.Wo1) {   // the o-projection slabs come from this launch's O1 stage
+                    if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_P0, (unsigned)(4 * (nw / 4)), tmo, 16u);
+                    wg_barrier();
+                }
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    if (t >= nr) continue;
+                    if (a.Wo1) fb_norm<FM_NS, true>(a.o1slab, M, r0 + t, d, a.post1_w, a.pre1_w, a.eps, hreg[t], a.xn1, nred);
+                    else fb_norm<FM_NS, false>(a.o_slabs, M, r0 + t, d, a.post1_w, a.pre1_w, a.eps, hreg[t], a.xn1, nred);
+                    if (tq < d / 8) hrow[t * HR + tq] = pack8f(hreg[t]);
+                }
+                fb_publish(cline(a.sync, L_N1), (unsigned)nr);
+                if constexpr (SELF) FS_TS(12);
+            }
+            {
+                if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_O0, (unsigned)(4 * (nw / 4)), tmo, 4u);
+                wg_barrier();
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    if (t >= nr) continue;
+                    float r2[8];
+                    unpack8f(hrow[t * HR + min(tq, d / 8 - 1)], r2);
+                    fb_norm<FM_NS, true>(a.oslab, M, r0 + t, d, a.post_w, a.pre_w, a.eps, r2, a.xn, nred);
+                    if (tq < d / 8) hrow[t * HR + tq] = pack8f(r2);
+                }
+                fb_publish(cline(a.sync, L_N2), (unsigned)nr);
+            }
+            {
+                if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_D0, (unsigned)(FM_DS * (nw / FM_DS)), tmo, 14u);
+                wg_barrier();
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    if (t >= nr) continue;
+                    float r3[8];
+                    unpack8f(hrow[t * HR + min(tq, d / 8 - 1)], r3);
+                    fb_norm<FM_DS, true>(a.dslab, M, r0 + t, d, a.post3_w, a.pre3_w, a.eps, r3, a.xn, nred);
+                    if (tq < d / 8) *(u32x4*)(a.h + (long)(r0 + t) * d + 8 * tq) = pack8f(r3);   // read by the next launch
+                }
+                fb_publish(cline(a.sync, L_N3), (unsigned)nr);
+            }
+            T5G_TS(6);
+            return;
         }
-        {
-            if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_O0, (unsigned)(4 * (nw / 4)), tmo, 4u);
-            wg_barrier();
-            float r2[8];
-            unpack8f(hrow[min(tq, d / 8 - 1)], r2);
-            fb_norm<FM_NS, true>(a.oslab, M, nrow, d, a.post_w, a.pre_w, a.eps, r2, a.xn, nred);
-            if (tq < d / 8) hrow[tq] = pack8f(r2);
-            fb_publish(cline(a.sync, L_N2), 1u);
-        }
-        {
-            if (wave == 0) ok &= fm_wait_split<8>(a.sync, L_D0, (unsigned)(FM_DS * (nw / FM_DS)), tmo, 14u);
-            wg_barrier();
-            float r3[8];
-            unpack8f(hrow[min(tq, d / 8 - 1)], r3);
-            fb_norm<FM_DS, true>(a.dslab, M, nrow, d, a.post3_w, a.pre3_w, a.eps, r3, a.xn, nred);
-            if (tq < d / 8) *(u32x4*)(a.h + (long)nrow * d + 8 * tq) = pack8f(r3);   // read by the next launch
-            fb_publish(cline(a.sync, L_N3), 1u);
-        }
-        T5G_TS(6);
-        return;
     }
     const int w = bu;   // worker index
     // gate/up: contiguous unit runs over the workers (<= 5 units, the last one from LDS)
@@ -1122,7 +1230,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     const int ubase = NGg / nw, uextra = NGg - ubase * nw;
     const int nu_g = ubase + (w < uextra ? 1 : 0);
     const int g_lo = w * ubase + min(w, uextra);
-    const bool gu_lds = nu_g > 0 && !attnwg;
+    const bool gu_lds = MT == 1 && nu_g > 0 && !attnwg;
     const int oper = nw / 4, so = w / oper, jo = w - so * oper;   // o-projection mapping (O1 and O)
     const bool owork = so < 4;
     const int nu_o = owork ? (a.NGo - jo + oper - 1) / oper : 0;
@@ -1135,7 +1243,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         fb_issue<8, 2, 3>(w1, a.Wo1, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
         if (SELF && wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_S0 + so, (unsigned)M, tmo, 17u);
         if constexpr (SELF) FS_TS_BY(9, (FM_NW - 1) * 64);
-        fb_finish<8, EPI_F32, 2, 3, 2>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
+        fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
                                        a.o1slab + (long)so * M * d, d, M * d * 4, d, red);
         fb_publish(cline(a.sync, L_P0 + (w & 7)), 1u);
         if constexpr (SELF) FS_TS(10);
@@ -1155,7 +1263,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N1, (unsigned)M, tmo, 1u);
             T5G_TS(1);
             if constexpr (SELF) FS_TS(11);
-            fb_finish<FM_NW, EPI_F32, 3, 2, 2>(wq, jq, qper, nu_q, sq * 36, 36, a.xn1, d, M * d * 2, M,
+            fb_finish<FM_NW, EPI_F32, 3, 2, 2, false, MT>(wq, jq, qper, nu_q, sq * 36, 36, a.xn1, d, M * d * 2, M,
                                                a.qslab + (long)sq * M * a.q_dim, a.q_dim, M * a.q_dim * 4, a.q_dim,
                                                red);
             drain_vm();
@@ -1183,16 +1291,18 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     }
 
     // ---- A (attention workers) with O's weight requests around it
+    // (two tiles: waves 4-7 run the pair's second head, so O's requests follow the attention)
     bf16x8_s wo[3][2];
-    if (attnwg && wave >= 4 && owork) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+    if (MT == 1 && attnwg && wave >= 4 && owork) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
     if (attnwg) {
         const int qcnt = 2 * (D / 16);   // 16 q units per head x 2 k-slices
-        if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_Q0 + ah, (unsigned)qcnt, tmo, 2u);
+        // (wave 0's head is the pair's first: two tiles poll both heads' lines at once)
+        if (wave == 0) ok &= fm_wait_n<MT>(a.sync, L_Q0 + ah, (unsigned)qcnt, tmo, 2u);
         wg_barrier();
         const int n = alen;
         const int span = alen;
-        if (tq < 256) {
-            const int c4 = tq < D / 4 ? tq : 0;
+        if (tq < 256 * MT) {
+            const int c4 = at < D / 4 ? at : 0;
             const int col = ah * D + 4 * c4;
             const __amdgpu_buffer_rsrc_t qr = raw_rsrc(a.qslab, (uint32_t)(2 * M * a.q_dim * 4));
             const f32x4 u0 = __builtin_bit_cast(
@@ -1200,13 +1310,13 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             const f32x4 u1 = __builtin_bit_cast(
                 f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, ((M + am) * a.q_dim + col) * 4, 0, AUX_SC1));
             const f32x4 acc = u0 + u1;
-            if (tq < D / 4) {
+            if (at < D / 4) {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) al.qs[4 * c4 + jj] = rbf(acc[jj]);
             }
         }
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (tq < 256) {
+        if (tq < 256 * MT) {
             float q[8];
             const float sg = dl < LPK / 2 ? -1.0f : 1.0f;
             const int pbase = (8 * dl + D / 2) % D;
@@ -1218,7 +1328,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             }
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
-                const int j = i * KPB + wave * KPW + kg;
+                const int j = i * KPB + aw * KPW + kg;
                 if (j >= n) {
                     kr[i] = (u32x4){0u, 0u, 0u, 0u};
                     vr[i] = (u32x4){0u, 0u, 0u, 0u};
@@ -1238,11 +1348,11 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             }
             if (dl == 0) {
 #pragma unroll
-                for (int i = 0; i < NIT; ++i) al.sm[i * KPB + wave * KPW + kg] = fast_score(scs[i], a.scale, a.softcap);
+                for (int i = 0; i < NIT; ++i) al.sm[i * KPB + aw * KPW + kg] = fast_score(scs[i], a.scale, a.softcap);
             }
         }
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (wave == 0) {
+        if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {   // a head's first wave
             const float sc = lane < n ? al.sm[lane] : -INFINITY;
             const float mx = wave_max(sc);
             const float p = lane < n ? sdpa_p(__fsub_rn(sc, mx), lane, span) : 0.f;
@@ -1254,13 +1364,13 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             if (lane == 0) al.stat_l = l;
         }
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (tq < 256) {
+        if (tq < 256 * MT) {
             float o[8];
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) o[jj] = 0.f;
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
-                const int jl = i * KPB + wave * KPW + kg;
+                const int jl = i * KPB + aw * KPW + kg;
                 const float p = al.sm[jl];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
@@ -1271,13 +1381,13 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) o[jj] += xlane32_v(o[jj]);   // LPK = 32: one xor-32 step
             if (kg == 0) {
-                al.ored[wave][dl][0] = (f32x4){o[0], o[1], o[2], o[3]};
-                al.ored[wave][dl][1] = (f32x4){o[4], o[5], o[6], o[7]};
+                al.ored[aw][dl][0] = (f32x4){o[0], o[1], o[2], o[3]};
+                al.ored[aw][dl][1] = (f32x4){o[4], o[5], o[6], o[7]};
             }
         }
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (tq < LPK && n > 0) {
-            const int d8 = tq;
+        if ((MT == 1 ? tq < LPK : (tq & ~256) < LPK) && n > 0) {
+            const int d8 = at;
             const f32x4 lo4 = al.ored[0][d8][0] + al.ored[1][d8][0] + al.ored[2][d8][0] + al.ored[3][d8][0];
             const f32x4 hi4 = al.ored[0][d8][1] + al.ored[1][d8][1] + al.ored[2][d8][1] + al.ored[3][d8][1];
             const float inv = __fdiv_rn(1.0f, al.stat_l);
@@ -1289,9 +1399,9 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             const __amdgpu_buffer_rsrc_t orr = raw_rsrc(a.att, (uint32_t)(M * a.q_dim * 2));
             __builtin_amdgcn_raw_buffer_store_b128(w, orr, (am * a.q_dim + ah * D + 8 * d8) * 2, 0, AUX_SC1);
         }
-        // only wave 0 stored: it drains and publishes (the other waves' O weight requests
-        // stay in flight)
-        if (wave == 0) {
+        // only a head's first wave stored: it drains and publishes (the other waves' O weight
+        // requests stay in flight)
+        if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {
             drain_vm();
             if (lane == 0) __hip_atomic_fetch_add(cline(a.sync, L_A0 + ah), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1301,17 +1411,17 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     if (owork) {
         // waves 0-7 (the GEMV) request their weights first; wave 11, idle in this stage and
         // with nothing queued, polls the 8 q heads
-        if (!(attnwg && wave >= 4)) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+        if (!(MT == 1 && attnwg && wave >= 4)) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
         if (wave == FM_NW - 1) ok &= fm_wait_n<8>(a.sync, L_A0, (unsigned)M, tmo, 3u);
         T5G_TS_BY(2, (FM_NW - 1) * 64);
-        fb_finish<8, EPI_F32, 2, 3, 2>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
+        fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
                                        a.oslab + (long)so * M * d, d, M * d * 4, d, red);
         fb_publish(cline(a.sync, L_O0 + (w & 7)), 1u);
     }
 
     // ---- G: gate/up, contiguous unit runs over the workers (<= 5 units; the last from LDS
     // on the workers that fetched it)
-    {
+    if constexpr (MT == 1) {
         bf16x8_s wg[5][6];
         const int nu_r = gu_lds ? nu_g - 1 : nu_g;
         fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
@@ -1319,6 +1429,12 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         T5G_TS(3);
         fb_finish<FM_NW, EPI_GEGLU, 6, 5, 0, true>(wg, g_lo, 1, nu_g, 0, KBg, a.xn, d, M * d * 2, M, a.act, f,
                                                    M * f * 2, 2 * f, red, gul, nu_r);
+    } else {
+        // two tiles: fused_mlp_kernel<2>'s stage (units streamed two batches deep, both tiles'
+        // partial sums in `red`), the first unit requested before the N2 wait
+        ok &= fm_gemv<MT, EPI_GEGLU, 6, 0>(
+            a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, M * d * 2, M, a.act, f, M * f * 2, 2 * f, red,
+            [&]() { return fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u); }, [](int) {}, 3);
     }
     T5G_TS(4);
     const int units_per_slice = f / FM_DS / 8;
@@ -1341,7 +1457,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper, nu_d);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_SL0 + s, (unsigned)units_per_slice, tmo, 6u + s);
         T5G_TS(5);
-        fb_finish<FM_NW, EPI_F32, 3, 5, 2>(wd, j, dper, nu_d, s * per, per, a.act, f, M * f * 2, M,
+        fb_finish<FM_NW, EPI_F32, 3, 5, 2, false, MT>(wd, j, dper, nu_d, s * per, per, a.act, f, M * f * 2, M,
                                            a.dslab + (long)s * M * d, d, M * d * 4, d, red);
         fb_publish(cline(a.sync, L_D0 + (w & 7)), 1u);
     }
@@ -1361,7 +1477,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
                 // its polls) waits for N3, then for every q|k|v workgroup
                 if (wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_N3, (unsigned)M, tmo, 15u);
                 FS_TS_BY(17, (FM_NW - 1) * 64);
-                fb_finish<FM_NW, EPI_F32, 3, 3, 2>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
+                fb_finish<FM_NW, EPI_F32, 3, 3, 2, false, MT>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
                                                    a.qkv_out + (long)sk * M * a.qkv_dim, a.qkv_dim,
                                                    M * a.qkv_dim * 4, a.qkv_dim, red);
                 fb_publish(cline(a.sync, L_K0 + (w & 7)), 1u);   // every worker (an odd one projects nothing)
@@ -1370,14 +1486,22 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
                 FS_TS_BY(19, (FM_NW - 1) * 64);
                 wg_barrier();
             };
-            fb_self_attn<true>(a, *(FbSelfLds*)gul, mid, nw, len_tail);
+            if constexpr (MT == 1) {
+                fb_self_attn<true>(a, *(FbSelfLds*)gul, mid, nw, len_tail);
+            } else {
+                // two tiles: the q|k|v stage first, then S with its K / V requests (held across
+                // the two-tile stage they do not fit the registers: 32 VGPRs spilled, and a
+                // request that is spilled has been waited for)
+                mid();
+                fb_self_attn<true>(a, *(FbSelfLds*)smem, [] {}, nw, len_tail);
+            }
             // the next layer's O1: k-slice so waits for kv head so's rows
             if (owork) {
                 bf16x8_s w1[3][2];
                 fb_issue<8, 2, 3>(w1, a.Wo1n, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
                 if (wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_S0 + so, (unsigned)M, tmo, 20u);
                 FS_TS_BY(20, (FM_NW - 1) * 64);
-                fb_finish<8, EPI_F32, 2, 3, 2>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
+                fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
                                                a.o1n + (long)so * M * d, d, M * d * 4, d, red);
                 FS_TS(21);
             }
@@ -1386,13 +1510,22 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             bf16x8_s wk[3][3];
             fb_issue<FM_NW, 3, 3>(wk, a.Wqkv, a.NGqkv, d / 32, sk * 36, 36, jk, kper, nu_k);
             if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N3, (unsigned)M, tmo, 15u);
-            fb_finish<FM_NW, EPI_F32, 3, 3, 1>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
+            fb_finish<FM_NW, EPI_F32, 3, 3, 1, false, MT>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
                                                a.qkv_out + (long)sk * M * a.qkv_dim, a.qkv_dim, 0, a.qkv_dim, red);
         }
     }
     (void)ok;
     T5G_TS(6);
 }
+
+typedef void (*fused_block_fn)(FusedMlpArgs);
+#ifdef T5G_FUSED_ROWS32
+// the two-tile kernel for stage S placement sv (0 none, 1 in front, 2 the tail)
+fused_block_fn fused_block_rows32_kernel(int sv) {
+    return sv == 2 ? fused_block_kernel<6> : sv ? fused_block_kernel<5> : fused_block_kernel<4>;
+}
+#else
+fused_block_fn fused_block_rows32_kernel(int sv);   // fused_rows32.hip
 
 constexpr size_t FM_LDS_MAX = 160 * 1024;
 
@@ -1424,14 +1557,19 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
     if (a.xattn) {
         // the cross-attention chain: 2 k-slices x NGq cross-q units = one unit-slice per
         // workgroup, 4 x 64 cross-o workgroups, 8 x 32 down workgroups; one 64-key chunk of
-        // text keys; attention and norm workgroups disjoint
-        const int nw = nb - a.M;   // workers (the last M workgroups run the norms)
+        // text keys; attention and norm workgroups disjoint. 17-32 rows (two tiles): a norm
+        // workgroup per two rows and an attention workgroup per (row, kv head) with its two q
+        // heads, so the same unit limits hold (nw >= 240 of 256)
+        const int nn = (a.M + MT - 1) / MT;
+        const int nw = nb - nn;   // workers (the last nn workgroups run the norms)
+        const int atasks = MT == 2 ? a.M * a.Hkv : a.M * a.Hq;
+        if (MT == 2 && a.Hq != 2 * a.Hkv) return -1;
         auto most = [](int units, int per) { return per > 0 ? (units + per - 1) / per : 1 << 20; };
-        if (MT != 1 || most(a.NGq, nw / 2) > 2 || most(a.NGo, nw / 4) > 3 || most(a.NGd, nw / FM_DS) > 5 ||
+        if (most(a.NGq, nw / 2) > 2 || most(a.NGo, nw / 4) > 3 || most(a.NGd, nw / FM_DS) > 5 ||
             most(a.NGgu, nw) > 5 || (a.Wqkv && most(a.NGqkv, nw / 2) > 3))
             return -1;
         if (a.D != 256 || a.Hq * a.D != a.q_dim || a.Hq % a.Hkv || a.Hq > 8 ||
-            a.NGq * 16 != a.q_dim || a.NGo * 16 != a.d || a.text_max > 64 || a.text_max > a.kv_cap || a.M * a.Hq > nw || !a.o_slabs ||
+            a.NGq * 16 != a.q_dim || a.NGo * 16 != a.d || a.text_max > 64 || a.text_max > a.kv_cap || atasks > nw || !a.o_slabs ||
             !a.post1_w || !a.pre1_w || !a.xn1 || !a.Wq || !a.qslab || !a.ck || !a.cv || !a.enc_len || !a.rope_tab ||
             !a.att || !a.Wo || !a.oslab)
             return -1;
@@ -1447,10 +1585,11 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
              a.M * a.Hkv * a.s_nsplit > FS_GRP * nb * FS_MAXPASS))   // <= 3 chunks per workgroup and pass
             return -1;
         if (a.Wqkv && (!a.qkv_out || a.NGqkv * 16 != a.qkv_dim)) return -1;
-        a.norm_b0 = nb - a.M;
+        a.norm_b0 = nb - nn;
+        static_assert(FB_LDS2 <= FM_LDS_MAX && sizeof(FbSelfLds) <= 2 * 5 * FM_NW * 1024, "two-tile LDS");
         static_assert(FB_GU_KB == FM_NW * 6 && FB_GU_KB % 3 == 0 && FB_LDS <= FM_LDS_MAX, "gate/up LDS unit");
         if (a.d != FB_D) return -1;
-        const size_t shm = FB_LDS;
+        const size_t shm = MT == 2 ? FB_LDS2 : FB_LDS;
         // function attributes and the occupancy check are per device (an engine per GPU in
         // one process must not skip the second device's hipFuncSetAttribute)
         if (dev < 0 || dev >= 64) return -1;
@@ -1462,17 +1601,18 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
              !a.sk || !a.sv || !a.kv_len || !a.fpart || !a.fstat || !a.fticket || a.Hq != 8 || a.Hkv != 4 ||
              a.D != FS_D || a.M > FS_MAXROWS || a.qkv_dim != a.q_dim + 2 * a.Hkv * a.D || a.s_cap < 1 ||
              a.s_nsplit < 1 || a.s_nsplit > DEC_MAX_CHUNKS || a.s_nsplit > (a.s_cap + FS_CH - 1) / FS_CH || a.window < 0 ||
-             a.M * a.Hkv * a.s_nsplit > 2 * (nb - a.M) || (long)a.M * a.Hkv * a.s_nsplit * FS_G * FS_D * 4 > 0x7fff0000L))
+             a.M * a.Hkv * a.s_nsplit > 2 * nw || (long)a.M * a.Hkv * a.s_nsplit * FS_G * FS_D * 4 > 0x7fff0000L))
             return -1;
         const int sv = a.self_tail ? 2 : a.self_attn ? 1 : 0;
-        auto* fb = sv == 2 ? fused_block_kernel<2> : sv ? fused_block_kernel<1> : fused_block_kernel<0>;
-        static bool attr_b[64][3] = {};
-        if (!attr_b[dev][sv]) {
+        fused_block_fn fb = MT == 2 ? fused_block_rows32_kernel(sv)
+                            : sv == 2 ? fused_block_kernel<2> : sv ? fused_block_kernel<1> : fused_block_kernel<0>;
+        static bool attr_b[64][2][3] = {};
+        if (!attr_b[dev][MT - 1][sv]) {
             (void)hipFuncSetAttribute((const void*)fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FM_LDS_MAX);
             int occ = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fb, FM_NW * 64, shm) != hipSuccess || occ < 1)
                 return -1;
-            attr_b[dev][sv] = true;
+            attr_b[dev][MT - 1][sv] = true;
         }
         if (!launch) return 0;
         hipLaunchKernelGGL(fb, dim3((unsigned)nb), dim3(FM_NW * 64), shm, st, a);
@@ -1496,5 +1636,6 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
     hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(FM_NW * 64), shm, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+#endif   // T5G_FUSED_ROWS32
 
 }  // namespace t5g

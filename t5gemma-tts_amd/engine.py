@@ -220,11 +220,25 @@ class T5GemmaTTSEngine:
     def set_fused(self, enable: bool) -> None:
         """Fast-path decode layer after the self attention (o-proj, norm, cross-q, cross
         attention, cross-o, norm, gate/up, down, norm, the next q|k|v) as one persistent
-        launch (default; 17-32 rows: the MLP half) or as per-op launches; bitwise equal
+        launch (default; 17-32 rows: the MLP half, or the whole layer with two MFMA tiles per
+        stage after set_block_max_rows(32)) or as per-op launches; bitwise equal
         (csrc/fused.hip). In parity mode the same switch selects the exact-order persistent
         layer (csrc/xlayer.hip; 1-8 rows of <= 64 text keys), bitwise equal to the per-op
         exact launches."""
         _lib.check(self.L.t5g_engine_set_fused(self.h, 1 if enable else 0), "set_fused")
+
+    def set_block_max_rows(self, n: int) -> None:
+        """The largest decode batch the whole-layer launch takes: 16 (default) or 32 (17-32
+        rows then run its two-tile form, csrc/fused_rows32.hip; bitwise equal to the per-op
+        launches). Other values raise ValueError."""
+        _lib.check(self.L.t5g_engine_set_block_max_rows(self.h, int(n)), "set_block_max_rows")
+
+    def block_launches(self) -> int:
+        """Fast-path whole-layer launches issued so far, with or without the self attention
+        inside (test / bench hook; a launch captured into a graph counts once)."""
+        n = C.c_int64()
+        _lib.check(self.L.t5g_engine_block_launches(self.h, C.byref(n)), "block_launches")
+        return n.value
 
     def xlayer_launches(self) -> int:
         """Parity-mode persistent layer launches issued so far (test / bench hook; a launch
