@@ -243,7 +243,7 @@ def lib():
     return _lib
 
 
-# The decode gate/up launch as engine.hip's decoder_pass issues it at the 2b-2b width
+# The decode gate/up launch as engine.hip's decode_pass issues it at the 2b-2b width
 # (gemv_dec with layout_rx: register-resident X, EPI_GEGLU, 8 waves sharing each unit's K
 # stream, 9 fragments per wave per unit, one block per CU).
 GATE_UP_KERNEL = "gemv_rx_kernel<12, 1, 3 (GEGLU), 6> (decode gate/up, M=8, 84.9 MB weights)"
@@ -269,7 +269,7 @@ PMC_SOURCES = {
     "gate_up": ["gemv.hip", "common.h", "t5g_kernels.h"],
     # every source the fast decode step's logits and tokens depend on (fast_token_agreement)
     "fast_path": ["fused.hip", "attn.hip", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
-                  "engine.hip", "common.h", "t5g_kernels.h"],
+                  "engine.hip", "engine_state.h", "common.h", "t5g_kernels.h"],
 }
 
 

@@ -8,143 +8,12 @@
 //   t5g_encode   -> :596-615 encoder + :198-230 cross K/V (computed once per call)
 //   t5g_prefill  -> :630-694 BOS+prompt decoder pass, :693 last hidden, :789 head
 //   t5g_decode   -> :788-848 loop body (sample_helper, embedding, decoder step)
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <string.h>
-#include <stdlib.h>
-
-#include <vector>
-
-#include "../../include/t5gtts.h"
-#include "ref_ksplit.h"
-#include "t5g_kernels.h"
-
-using namespace t5g;
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        if ((x) != hipSuccess) return T5G_EHIP;    \
-    } while (0)
-#define RC(x)                       \
-    do {                            \
-        int _rc = (x);              \
-        if (_rc) return _rc == -1 ? T5G_EINVAL : (_rc == -3 ? T5G_EUNSUPPORTED : T5G_EHIP); \
-    } while (0)
+//
+// The engine's state is engine_state.h; the timing hooks (t5g_time_*) and the stand-alone op
+// wrappers for tests and probes are engine_hooks.hip.
+#include "engine_state.h"
 
 constexpr int GRAPH_STEPS = 8;   // decode iterations per multi-step graph
-
-static inline int ng_pad(int N) { return ((N + 15) / 16 + 3) / 4 * 4; }
-
-struct t5g_engine {
-    t5g_config c;
-    t5g_weights w;
-    std::vector<t5g_layer_weights> enc, dec;
-    int q_dim, kv_dim, qkv_dim, V, Vpad;
-    int max_tok;  // packed token capacity for encode / prefill
-    // arena
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
-    // packed-token activations (encode / prefill)
-    bf16_t *h, *xn, *qkv, *q, *att, *act, *tmp, *mem;
-    float* part;          // split-K slabs (max over uses)
-    int64_t part_elems;
-    bf16_t *enc_k, *enc_v;                 // encoder self K/V [B][Hkv][max_text][D]
-    std::vector<bf16_t*> ck, cv, sk, sv;   // per decoder layer cross / self caches
-    int* enc_len;                          // [B] text lengths
-    // decode (rows = max_batch)
-    bf16_t *dh, *dxn, *dq, *datt, *dact, *dhh, *logits;
-    int logits_ld;
-    // sampler
-    SamplerRow* rows;
-    SamplerState* state;
-    int* topk_list;
-    int* silence;
-    int* out_tokens;
-    int* kv_len;
-    float* next_pos;
-    int* next_token;
-    int* flags;
-    int* last_rows;
-    float* rope_tab;    // [max_batch][D] per-row cos|sin of the decode step's PM position
-    // multi-block sampler scratch (sampler.hip fast path)
-    float* fs_val;
-    int* fs_idx;
-    int* fs_cnt;
-    float* fs_amv;
-    int* fs_ami;
-    unsigned* fs_ticket;
-    int* fs_slow;
-    bool fast_sampler = true;   // false: single-block sampler only (t5g_engine_set_sampler_path)
-    // decode MLP half as one persistent launch (fused.hip; t5g_engine_set_fused)
-    bool fused_mlp = true;
-    float* part2 = nullptr;     // the fused block's in-launch slabs: cross-q [2][B][q_dim] | cross-o [4][B][d] | down [8][B][d] | self o [4][B][d]
-    bf16_t* datt2 = nullptr;    // the fused block's cross-attention output [B][q_dim]
-    unsigned* fsync = nullptr;  // timeout line + one fused.hip counter set per decoder layer + one xlayer.hip
-                                // set per decoder layer (zeroed at creation / after a timeout)
-    // decode split-K factors (measured on MI355X): qkv 2, o / cross-q /
-    // cross-o 4, down 8 k-slices; gate/up on the one-block-per-CU GEMV
-    static constexpr int s_qkv = 2, s_o = 4, s_down = 8;
-    float* asbuf = nullptr;   // decode attention scores of rows > 64 keys [B][Hq][max(max_audio, max_text)]
-    float* ambuf = nullptr;   // decode attention chunk maxima [B][Hkv][nsplit][G]
-    // flash-form decode attention (fast path, t5g_engine_set_attn_flash): chunk partials,
-    // chunk (max, sum), one arrival ticket per (row, kv head) -- zeroed here, left zero
-    bool attn_flash = true;
-    // the flash decode self-attention as stage S of the persistent layer launch (fast path,
-    // t5g_engine_set_attn_in_block): no attention launch of its own between the layers
-    int attn_in_block = 2;   // 0 own launch, 1 stage S in front of O1, 2 at the end of the previous launch
-    // the largest batch the whole-layer launch takes (t5g_engine_set_block_max_rows): 16 (one
-    // MFMA tile) or 32 (two tiles, fused_rows32.hip); larger batches run the per-op launches
-    // with the MLP-half launch
-    int block_max_rows = 16;
-    int64_t blk_launches = 0;   // whole-layer launches issued (t5g_engine_block_launches)
-    int64_t s_launches = 0;   // persistent layer launches run with stage S (tests)
-    int s_mode_used = 0;      // the last decode pass's stage-S placement: 2 tail, 1 front, 0 none
-    float* afpart = nullptr;    // [B][Hkv][nsplit][G][D]
-    float* afstat = nullptr;    // [B][Hkv][nsplit][G][2]
-    unsigned* aftick = nullptr; // [B][Hkv]
-    int B = 0;            // rows of the current call
-    int text_max = 0;     // longest text of the current call (host hint; 0: max_text)
-    int audio_max = 0;    // key bound of the current call's rows (host hint; 0: max_audio)
-    const bf16_t* noise = nullptr;
-    int noise_steps = 0;
-    const uint32_t* noise_mt = nullptr;   // parity mode: raw MT19937 outputs [B][noise_mt_steps][2 V] (noise.hip)
-    int noise_mt_steps = 0;
-    // graphs of one and of GRAPH_STEPS decode iterations (a replay boundary costs
-    // ~10 us; back-to-back iterations inside one graph only the kernel boundaries)
-    hipGraph_t graph = nullptr, graph_n = nullptr;
-    hipGraphExec_t gexec = nullptr, gexec_n = nullptr;
-    int graph_B = -1;
-    // graph of one decoder step + head without the sampler (t5g_step_only: parity mode)
-    hipGraph_t graph_fwd = nullptr;
-    hipGraphExec_t gexec_fwd = nullptr;
-    int graph_fwd_B = -1;
-    hipStream_t graph_stream = nullptr;
-    hipStream_t cap_stream = nullptr;
-    // parity mode (t5g_engine_set_exact): every sum in the reference host's CPU order
-    bool exact = false;
-    int exact_threads = REF_KSPLIT_THREADS;
-    uint16_t* ksplit_dev = nullptr;     // ref_ksplit.h tables [REF_KSPLIT_NSHAPES][REF_KSPLIT_MAX_M]
-    uint16_t* gelu_lut_dev = nullptr;   // [65536] bf16 -> bf16 nn.GELU() of the reference host
-    uint16_t* tanh_lut_dev = nullptr;   // [65536] bf16 -> bf16 torch.tanh of the reference host (eager)
-    // parity mode's Linears on the f32 MFMA (xmm.hip): E16 copies of the packed weights
-    // (made once, at the first t5g_engine_set_exact) and X16 activation buffers
-    struct XLayer {
-        bf16_t *qkv, *o, *gate_up, *down, *cross_q, *cross_kv, *cross_o;
-    };
-    std::vector<XLayer> enc_x, dec_x;
-    bf16_t *head1_x = nullptr, *head2_x = nullptr;
-    bf16_t *xn16 = nullptr, *att16 = nullptr, *act16 = nullptr, *mem16 = nullptr;   // packed tokens
-    bf16_t *dxn16 = nullptr, *datt16 = nullptr, *dact16 = nullptr, *dhh16 = nullptr;   // decode rows
-    float* dpart = nullptr;   // decode down projection: fp32 K-part values [4][B16][hidden]
-    uint32_t* trig_exc = nullptr;   // parity mode: RoPE cos / sin exceptions (t5g_engine_set_rope_exc)
-    int n_trig_exc = 0;
-    bool xmm_ready = false;
-    // the timing hooks (t5g_time_*) re-run launches on the live decode state (h, the KV slot
-    // of the last step, the attention scratch): t5g_decode refuses to continue from it until a
-    // t5g_sampler_setup (after a fresh prefill) starts a new call
-    bool decode_state_invalid = false;
-    int64_t xl_launches = 0;   // xlayer.hip launches issued (captured ones counted once, at capture)
-};
 
 // words of e->fsync: the timeout line, the fused.hip sets, the xlayer.hip sets
 static size_t fsync_words(const t5g_config& c) {
@@ -186,6 +55,30 @@ static void drop_graphs(t5g_engine* e) {
     if (e->graph_fwd) hipGraphDestroy(e->graph_fwd);
     e->gexec = e->gexec_n = e->gexec_fwd = nullptr;
     e->graph = e->graph_n = e->graph_fwd = nullptr;
+}
+
+// The launches body(stream) issues, captured on the engine's capture stream and instantiated.
+// On failure *graph / *exec are untouched and nothing is left behind; what happens to the
+// engine's other graphs is the caller's business.
+template <typename F>
+static int capture(t5g_engine* e, F body, hipGraph_t* graph, hipGraphExec_t* exec) {
+    if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = body(e->cap_stream);
+    hipGraph_t g = nullptr;
+    const hipError_t ec = hipStreamEndCapture(e->cap_stream, &g);
+    if (rc || ec != hipSuccess) {
+        if (g) hipGraphDestroy(g);
+        return rc ? rc : T5G_EHIP;
+    }
+    hipGraphExec_t x = nullptr;
+    if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
+        hipGraphDestroy(g);
+        return T5G_EHIP;
+    }
+    *graph = g;
+    *exec = x;
+    return T5G_OK;
 }
 
 extern "C" int t5g_engine_destroy(t5g_engine* e) {
@@ -300,8 +193,8 @@ extern "C" int t5g_engine_create(const t5g_config* cfg, const t5g_weights* w, t5
 // to run: a wave could reach the ring's barrier with its own ds_reads of the slot still in
 // flight while the DMA refilled it; the barrier now waits for lgkmcnt(0) too (gemm.hip
 // wait_vm_barrier; tests/test_gpu_prefill_lds.py, tools/diag_det_logits.py).
-static int gemm(const bf16_t* X, int ldx, int M, const void* W, int N, int K, int splits, const void* bias,
-                void* Y, int ldy, int epi, hipStream_t st, bool prefill = false, bool pf_reg = false) {
+int gemm(const bf16_t* X, int ldx, int M, const void* W, int N, int K, int splits, const void* bias, void* Y, int ldy,
+         int epi, hipStream_t st, bool prefill, bool pf_reg) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.prefill = prefill ? (pf_reg ? 2 : 1) : 0;
@@ -319,7 +212,7 @@ static int gemm(const bf16_t* X, int ldx, int M, const void* W, int N, int K, in
     return gemm_p16(a, epi, st);
 }
 
-static NormArgs norm_args(int M, int d, float eps) {
+NormArgs norm_args(int M, int d, float eps) {
     NormArgs n;
     memset(&n, 0, sizeof(n));
     n.M = M;
@@ -374,9 +267,9 @@ static const uint16_t* ksplit_tab(const t5g_engine* e, int N, int K) {
 // Exact Linear on the f32 MFMA: X16 operand, E16 weights; Y row-major and / or Y16.
 // nref_a / nref_b: the reference Linear's output width for packed columns < / >= nsplit_col
 // (q | k,v share one packed matrix here but are separate F.linear calls there)
-static int xlin16(t5g_engine* e, const bf16_t* X16, int M, const bf16_t* W16, int N, int K, const void* bias,
-                  void* Y, int ldy, bf16_t* Y16, int epi, const int* tok_row, const int* row_len, int nref_a,
-                  int nref_b, int nsplit_col, hipStream_t st) {
+int xlin16(t5g_engine* e, const bf16_t* X16, int M, const bf16_t* W16, int N, int K, const void* bias, void* Y,
+           int ldy, bf16_t* Y16, int epi, const int* tok_row, const int* row_len, int nref_a, int nref_b,
+           int nsplit_col, hipStream_t st) {
     XmmArgs a;
     memset(&a, 0, sizeof(a));
     a.X16 = X16;
@@ -413,8 +306,8 @@ static int ksplit_host(int N, int K, int M) {
 // workgroup per (group, part) writes the parts' fp32 values to e->dpart and the number of
 // parts is returned in *nparts (the consumer norm folds them); otherwise a plain bf16 Linear
 // into Y (*nparts = 0).
-static int xlin16_dec_parts(t5g_engine* e, const bf16_t* X16, int M, const bf16_t* W16, int N, int K, void* Y,
-                            int ldy, const int* tok_row, int* nparts, hipStream_t st) {
+int xlin16_dec_parts(t5g_engine* e, const bf16_t* X16, int M, const bf16_t* W16, int N, int K, void* Y, int ldy,
+                     const int* tok_row, int* nparts, hipStream_t st) {
     const int kbc = ksplit_host(N, K, 1), KB = K / 32;
     *nparts = 0;
     if (kbc >= KB || M > 32 || (KB + kbc - 1) / kbc > 4 || N > e->c.hidden)
@@ -610,7 +503,7 @@ static int encode_exact(t5g_engine* e, int ntok, const int32_t* ids, const int32
 // the 2b-2b shapes, M <= 8 rows, <= 64 text keys per row (the call's hint), no softcap, and
 // the reference splitting none of the layer's M = 1 Linears but the down projection, in two
 // K parts of 144 chunks (ref_ksplit.h) -- the arithmetic the launch is built for
-static bool xlayer_usable(const t5g_engine* e, int M) {
+bool xlayer_usable(const t5g_engine* e, int M) {
     const t5g_config& c = e->c;
     if (!e->fused_mlp || M < 1 || M > 8 || c.softcap > 0.f || c.n_dec_layers < 2) return false;
     if (c.hidden != 2304 || c.intermediate != 9216 || e->q_dim != 2048 || e->kv_dim != 1024 || c.head_dim != 256 ||
@@ -622,7 +515,7 @@ static bool xlayer_usable(const t5g_engine* e, int M) {
            ksplit_host(2304, 9216, 1) == 144;
 }
 
-static XLayerArgs xlayer_args(t5g_engine* e, int M, int l) {
+XLayerArgs xlayer_args(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
     const t5g_layer_weights& L = e->dec[l];
     const t5g_engine::XLayer& X = e->dec_x[l];
@@ -1041,9 +934,21 @@ extern "C" int t5g_encode(t5g_engine* e, int32_t B, int32_t ntok, const int32_t*
     return T5G_OK;
 }
 
-// One decoder pass over `M` tokens. Packed mode (tok_row != null): prefill;
-// decode mode: M = B rows, positions/slots/tokens from the sampler buffers.
-static DecGemmArgs dec_args(int M, const void* W, int N, int K, void* Y, int ldy, int nw);
+DecGemmArgs dec_args(int M, const void* W, int N, int K, void* Y, int ldy, int nw) {
+    DecGemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.M = M;
+    g.K = K;
+    g.W = (const bf16_t*)W;
+    g.N = N;
+    g.NG = ng_pad(N);
+    g.KB = K / 32;
+    g.Y = Y;
+    g.ldy = ldy;
+    g.nw = nw;
+    g.splits = 1;
+    return g;
+}
 
 // decode attention over a per-layer cache (self: the step's k/v appended in-kernel)
 static int decode_attention(t5g_engine* e, int M, const bf16_t* K, const bf16_t* Vc, int cap, const int* kv_len,
@@ -1092,7 +997,7 @@ static int decode_attention(t5g_engine* e, int M, const bf16_t* K, const bf16_t*
 
 // the decode MLP half of decoder layer l as one persistent launch (fused.hip): cross-o
 // slabs in e->part -> h / xn -> act -> down slabs in e->part; layer l's counter set
-static FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
+FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
     const t5g_layer_weights& L = e->dec[l];
     FusedMlpArgs fa;
@@ -1120,7 +1025,7 @@ static FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
 
 // the same launch with the cross-attention chain in front (fused.hip fused_block_kernel):
 // o-proj slabs in e->part -> ... -> down slabs in e->part
-static FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
+FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
     const t5g_layer_weights& L = e->dec[l];
     FusedMlpArgs fa = fused_args(e, M, l);
@@ -1162,9 +1067,8 @@ static FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
     return fa;
 }
 
-// stage S in front (fast path): the layer's flash decode self-attention inside the launch,
-// with decode_attention's arguments (the cache, the call's chunk grid, the q|k|v slabs);
-// false when the launch is not built for them (the attention then runs as its own launch)
+// stage S (fast path): layer l's flash decode self-attention inside the launch, with
+// decode_attention's arguments (the cache, the call's chunk grid, the q|k|v slabs)
 static void fused_s_fields(t5g_engine* e, int l, FusedMlpArgs& fa) {
     const t5g_config& c = e->c;
     fa.qkv_in = e->part;
@@ -1184,7 +1088,7 @@ static void fused_s_fields(t5g_engine* e, int l, FusedMlpArgs& fa) {
 // runs its self attention and its o-projection into the o1slab region, which the next
 // launch's N1 reads as o_slabs (layer 0's come from the step's prologue in e->part);
 // false when the launch is not built for them
-static bool fused_block_tail(t5g_engine* e, int M, int l, FusedMlpArgs& fa) {
+bool fused_block_tail(t5g_engine* e, int l, FusedMlpArgs& fa) {
     const t5g_config& c = e->c;
     fa.Wo1 = nullptr;   // the o-projection of this layer ran at the end of the previous launch
     fa.o_slabs = l == 0 ? e->part : fa.o1slab;
@@ -1194,86 +1098,98 @@ static bool fused_block_tail(t5g_engine* e, int M, int l, FusedMlpArgs& fa) {
     fa.Wo1n = (const bf16_t*)e->dec[l + 1].o;
     fa.o1n = fa.o1slab;
     fa.att_self = e->datt;
-    (void)M;
     return fused_mlp_check(fa) == 0;
 }
 
-static bool fused_block_self(t5g_engine* e, int M, int l, FusedMlpArgs& fa) {
-    const t5g_config& c = e->c;
+// stage S in front of layer l's o-projection; false when the launch is not built for it (the
+// attention then runs as its own launch)
+static bool fused_block_self(t5g_engine* e, int l, FusedMlpArgs& fa) {
     // mode 1, or mode 2 on a call the tail does not take (2 slots per worker): S in front
     if (e->attn_in_block < 1 || !e->attn_flash || !fa.Wo1) return false;
     fa.self_attn = 1;
-    fa.qkv_in = e->part;
-    fa.sk = e->sk[l];
-    fa.sv = e->sv[l];
-    fa.s_cap = c.max_audio;
-    fa.s_nsplit = (c.max_audio + 63) / 64;
-    if (e->audio_max > 0 && e->audio_max < c.max_audio) fa.s_nsplit = (e->audio_max + 63) / 64;
-    fa.kv_len = e->kv_len;
-    fa.window = c.dec_sliding[l] ? c.sliding_window : 0;
-    fa.fpart = e->afpart;
-    fa.fstat = e->afstat;
-    fa.fticket = e->aftick;
-    if (fused_mlp_check(fa) != 0) {
-        fa.self_attn = 0;
-        return false;
-    }
-    (void)M;
-    return true;
+    fused_s_fields(e, l, fa);
+    return fused_mlp_check(fa) == 0;
 }
 
-static int decoder_pass(t5g_engine* e, int M, const int* ids, const int* tok_row, const int* tok_t, const float* pos,
-                        bool decode, hipStream_t st) {
+DecodePlan decode_plan(t5g_engine* e, int M, int block_rows, bool switches) {
+    const t5g_config& c = e->c;
+    // the 2b-2b widths, each named by the Linears whose K or N it is
+    const bool wd = c.hidden == 2304, wf = c.intermediate == 9216, wq = e->q_dim == 2048;
+    const bool rows32 = M <= 32;   // the register-X GEMVs and the MLP-half launch: two 16-row tiles
+    const GemvSite gemm_only = {0, 0, 0, false};
+    DecodePlan p;
+    // register-X GEMVs, so a row's sums never depend on the batch. q|k|v and cross-q: 12 waves
+    // over 2 k-slices of 36 k-steps (the fused block's QKV / Q stages); o and cross-o: 4 slices
+    // of 16 k-steps (tools/probe_proj_rx.py: 4.13 vs 4.23 us at 8 rows, 5.2 vs 6.8 at 32);
+    // down: 36-k-step slices, 32 blocks per slice (tools/probe_down_rx.py: 11.2 vs 16.3 us at
+    // 32 rows, 9.0 vs 9.4 at 8)
+    p.qkv = rows32 && wd ? GemvSite{12, e->s_qkv, 0, true} : gemm_only;
+    p.proj = rows32 && wd && wq ? GemvSite{8, e->s_o, 0, true} : gemm_only;
+    p.cross_q = rows32 && wd && wq ? GemvSite{12, 2, 0, true} : gemm_only;
+    p.down = rows32 && wd && wf ? GemvSite{12, e->s_down, 0, true} : gemm_only;
+    // gate/up on the one-block-per-CU GEMV; register-X at the 2b-2b width, every unit's weights
+    // requested up front (18.84 -> 18.39 us at 8 rows, 24.2 -> 23.9 at 32, bitwise equal:
+    // tools/probe_rx_all.py)
+    p.gate_up = rows32 && wd ? GemvSite{12, 1, -1, true} : M <= 16 ? GemvSite{8, 1, 8, false} : gemm_only;
+    p.mlp_half = e->fused_mlp && rows32 && wd && wf && c.n_dec_layers >= 2;
+    p.block = M <= block_rows && (!switches || (p.mlp_half && wq));
+    // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
+    p.tail = p.block && e->attn_in_block == 2 && (!switches || e->attn_flash);
+    for (int l = 0; l < c.n_dec_layers && p.tail; ++l) {
+        FusedMlpArgs fa = fused_block_args(e, M, l);
+        p.tail = fused_block_tail(e, l, fa);
+    }
+    return p;
+}
+
+DecodeLaunch decode_layer_launch(t5g_engine* e, const DecodePlan& p, int M, int l, FusedMlpArgs& fa) {
+    if (p.block) {
+        fa = fused_block_args(e, M, l);
+        if (fused_mlp_check(fa) == 0) {
+            FusedMlpArgs s = fa;   // fa stays the launch without S when S is refused
+            if (!fused_block_self(e, l, s)) return DL_BLOCK;
+            fa = s;
+            return DL_BLOCK_S;
+        }
+    }
+    if (!p.mlp_half) return DL_PER_OP;
+    fa = fused_args(e, M, l);
+    return DL_MLP_HALF;
+}
+
+// layer 0's input: the embedded tokens, normed for the self attention
+static NormArgs embed_norm_args(const t5g_engine* e, int M, const int* ids, bf16_t* h, bf16_t* xn) {
+    const t5g_config& c = e->c;
+    NormArgs n = norm_args(M, c.hidden, c.rms_eps);
+    n.ids = ids;
+    n.table = (const bf16_t*)e->w.audio_embed;
+    n.n_table = c.n_audio_tokens;
+    n.scale = c.normalizer;
+    n.pre_w = (const bf16_t*)e->dec[0].norms[0];
+    n.resid_out = h;
+    n.normed_out = xn;
+    return n;
+}
+
+// One decoder pass over M packed tokens (prefill): tiled GEMMs with bf16 outputs, RoPE and the
+// cache stores in rope_store, packed attention.
+static int prefill_pass(t5g_engine* e, int M, const int* ids, const int* tok_row, const int* tok_t, const float* pos,
+                        hipStream_t st) {
     const t5g_config& c = e->c;
     const int d = c.hidden, f = c.intermediate, D = c.head_dim;
-    bf16_t* h = decode ? e->dh : e->h;
-    bf16_t* xn = decode ? e->dxn : e->xn;
-    bf16_t* q = decode ? e->dq : e->q;
-    bf16_t* att = decode ? e->datt : e->att;
-    bf16_t* act = decode ? e->dact : e->act;
-    bf16_t* tmp = e->tmp;
-    // eager checkpoints (softcap > 0) take the same decode launches: the attention kernels
-    // apply the tanh softcap in the score (common.h fast_score)
-    // split-K factors (decode: spread the weight streams over >= 512 blocks)
-    const int s_qkv = decode ? e->s_qkv : 1, s_o = decode ? e->s_o : 1, s_down = decode ? e->s_down : 1;
-    // one cos/sin table per step: every layer's q/k rotation uses the same positions
-    // (written by layer 0's embedding-norm launch below)
-    const float* tab = decode ? e->rope_tab : nullptr;
-    // norm after a Linear: h = h + RMSNorm_post(delta), xn = RMSNorm_pre(h)
-    auto resid = [&](int splits, const void* post_w, const void* pre_w) -> int {
-        NormArgs n = norm_args(M, d, c.rms_eps);
-        if (splits > 1) {
-            n.part = e->part;
-            n.nsplit = splits;
-            n.ldp = d;
-        } else {
-            n.delta = tmp;
-        }
-        n.post_w = (const bf16_t*)post_w;
-        n.resid = h;
-        n.pre_w = (const bf16_t*)pre_w;
-        n.resid_out = h;
-        n.normed_out = xn;
-        return resid_norm(n, st);
+    // a Linear into tmp, then h = h + RMSNorm_post(tmp), xn = RMSNorm_pre(h)
+    auto linear = [&](const bf16_t* x, int K, const void* W) -> int {
+        return gemm(x, K, M, W, d, K, 1, nullptr, e->tmp, d, EPI_BF16, st, true);
     };
-    // attention output projection into the norm's fp32 slabs: at the 2b-2b width (K = 2048,
-    // 4 slices of 16 k-steps) on the register-resident-X GEMV for every batch size up to 32,
-    // so a row's sums never depend on the batch (tools/probe_proj_rx.py: 4.13 vs 4.23 us at
-    // 8 rows, 5.2 vs 6.8 at 32)
-    auto out_proj = [&](const bf16_t* x, const void* W) -> int {
-        if (decode && M <= 32 && d == 2304 && e->q_dim == 2048 && s_o == 4) {
-            DecGemmArgs g = dec_args(M, W, d, e->q_dim, e->part, d, 8);
-            g.X = x;
-            g.ldx = e->q_dim;
-            g.splits = s_o;
-            g.layout_rx = 1;
-            // -1: the register-X GEMV's per-block LDS does not fit this device's CU count
-            // (e.g. a CPX partition): the tiled split-K GEMM below
-            const int rc = gemv_dec(g, EPI_F32, st);
-            if (rc != -1) return rc;
-        }
-        return gemm(x, e->q_dim, M, W, d, e->q_dim, s_o, nullptr, s_o > 1 ? (void*)e->part : (void*)tmp, d,
-                    s_o > 1 ? EPI_F32 : EPI_BF16, st, !decode);
+    auto resid = [&](const void* post_w, const void* pre_w) -> int {
+        NormArgs n = norm_args(M, d, c.rms_eps);
+        n.delta = e->tmp;
+        n.post_w = (const bf16_t*)post_w;
+        n.resid = e->h;
+        n.pre_w = (const bf16_t*)pre_w;
+        n.resid_out = e->h;
+        n.normed_out = e->xn;
+        return resid_norm(n, st);
     };
     auto rope_args = [&]() {
         RopeArgs r;
@@ -1285,228 +1201,188 @@ static int decoder_pass(t5g_engine* e, int M, const int* ids, const int* tok_row
         r.tok_row = tok_row;
         r.tok_t = tok_t;
         r.kv_len = e->kv_len;
-        r.rope_tab = tab;
-        r.Qout = q;
+        r.Qout = e->q;
         r.ldq = e->q_dim;
         return r;
     };
-    bool qkv_done = false;   // the previous layer's fused block projected this layer's q|k|v
-    // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
-    bool tail = false;
-    if (decode && e->attn_in_block == 2 && e->attn_flash && e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 &&
-        s_o == 4 && s_down == 8 && s_qkv == 2 && e->q_dim == 2048 && c.n_dec_layers >= 2) {
-        tail = true;
-        for (int l = 0; l < c.n_dec_layers && tail; ++l) {
-            FusedMlpArgs fa = fused_block_args(e, M, l);
-            tail = fused_block_tail(e, M, l, fa);
-        }
-    }
-    if (decode) e->s_mode_used = tail ? 2 : 0;
+    RC(resid_norm(embed_norm_args(e, M, ids, e->h, e->xn), st));
     for (int l = 0; l < c.n_dec_layers; ++l) {
         const t5g_layer_weights& L = e->dec[l];
-        if (l == 0) {
-            NormArgs n = norm_args(M, d, c.rms_eps);
-            n.ids = ids;
-            n.table = (const bf16_t*)e->w.audio_embed;
-            n.n_table = c.n_audio_tokens;
-            n.scale = c.normalizer;
-            n.pre_w = (const bf16_t*)L.norms[0];
-            n.resid_out = h;
-            n.normed_out = xn;
-            if (decode) {   // and the step's RoPE table, in the same launch
-                n.rope_pos = pos;
-                n.rope_inv_freq = e->w.inv_freq;
-                n.rope_tab = e->rope_tab;
-                n.rope_D = D;
-            }
-            RC(resid_norm(n, st));
-        }
-        // --- self attention
-        const int win = c.dec_sliding[l] ? c.sliding_window : 0;
-        if (decode) {
-            // q|k|v as fp32 split-K slabs; q rotated, k rotated + appended inside attention.
-            // At the 2b-2b width: the 12-wave register-X GEMV over 2 k-slices (the fused
-            // block's QKV stage, which produced them already when qkv_done)
-            if (!qkv_done) {
-                int rcq = -1;
-                if (M <= 32 && d == 2304 && s_qkv == 2) {
-                    DecGemmArgs g = dec_args(M, L.qkv, e->qkv_dim, d, e->part, e->qkv_dim, 12);
-                    g.X = xn;
-                    g.ldx = d;
-                    g.splits = 2;
-                    g.layout_rx = 1;
-                    rcq = gemv_dec(g, EPI_F32, st);
-                    if (rcq != 0 && rcq != -1) RC(rcq);
-                }
-                if (rcq != 0) RC(gemm(xn, d, M, L.qkv, e->qkv_dim, d, s_qkv, nullptr, e->part, e->qkv_dim, EPI_F32, st));
-            }
-            qkv_done = false;
-            if (tail) {
-                // layer 0's attention and o-projection as their own launches (the step's
-                // prologue), then every layer's launch runs the next layer's attention and
-                // o-projection at its end (bitwise equal to the launches below)
-                if (l == 0) {
-                    RC(decode_attention(e, M, e->sk[l], e->sv[l], c.max_audio, e->kv_len, 1, win, 0, true, pos, tab,
-                                        s_qkv, e->qkv_dim, st));
-                    RC(out_proj(att, L.o));
-                }
-                FusedMlpArgs fa = fused_block_args(e, M, l);
-                if (!fused_block_tail(e, M, l, fa)) return T5G_EUNSUPPORTED;   // checked for every layer above
-                RC(fused_mlp(fa, st));
-                ++e->blk_launches;
-                if (l != c.n_dec_layers - 1) ++e->s_launches;
-                qkv_done = true;
-                continue;
-            }
-            // the persistent layer launch with the attention as its stage S (bitwise equal to
-            // the flash launch below followed by the same launch without S)
-            if (e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 && s_qkv == 2 &&
-                e->q_dim == 2048 && c.n_dec_layers >= 2) {
-                FusedMlpArgs fa = fused_block_args(e, M, l);
-                if (fused_mlp_check(fa) == 0 && fused_block_self(e, M, l, fa)) {
-                    RC(fused_mlp(fa, st));
-                    ++e->blk_launches;
-                    ++e->s_launches;
-                    e->s_mode_used = 1;
-                    qkv_done = l != c.n_dec_layers - 1;
-                    continue;
-                }
-            }
-            RC(decode_attention(e, M, e->sk[l], e->sv[l], c.max_audio, e->kv_len, 1, win, 0, true, pos, tab, s_qkv,
-                                e->qkv_dim, st));
-        } else {
-            RC(gemm(xn, d, M, L.qkv, e->qkv_dim, d, 1, nullptr, e->qkv, e->qkv_dim, EPI_BF16, st, !decode));
-            RopeArgs r = rope_args();
-            r.X = e->qkv;
-            r.ldx = e->qkv_dim;
-            r.nq = c.n_heads;
-            r.nk = r.nv = c.n_kv_heads;
-            r.rope_q = r.rope_k = 1;
-            r.Kc = e->sk[l];
-            r.Vc = e->sv[l];
-            r.c_hstride = (long)c.max_audio * D;
-            r.c_bstride = r.c_hstride * c.n_kv_heads;
-            RC(rope_store(r, st));
-            RC(attn_packed(e, M, q, tok_row, tok_t, e->sk[l], e->sv[l], c.max_audio, e->kv_len, 1, win, att, st));
-        }
         const bool last = l == c.n_dec_layers - 1;
-        // the rest of the layer (o-projection, cross attention, MLP half, the last norm and
-        // the next layer's q|k|v) as one persistent launch (fused.hip fused_block_kernel;
-        // bitwise equal to the launches below)
-        if (decode && e->fused_mlp && M <= e->block_max_rows && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 &&
-            e->q_dim == 2048 && c.n_dec_layers >= 2) {
-            const FusedMlpArgs fa = fused_block_args(e, M, l);
-            if (fused_mlp_check(fa) == 0) {
-                RC(fused_mlp(fa, st));
-                ++e->blk_launches;
-                qkv_done = !last;
-                continue;
-            }
-        }
-        RC(out_proj(att, L.o));
-        RC(resid(s_o, L.norms[1], L.norms[2]));
+        // --- self attention
+        RC(gemm(e->xn, d, M, L.qkv, e->qkv_dim, d, 1, nullptr, e->qkv, e->qkv_dim, EPI_BF16, st, true));
+        RopeArgs r = rope_args();
+        r.X = e->qkv;
+        r.ldx = e->qkv_dim;
+        r.nq = c.n_heads;
+        r.nk = r.nv = c.n_kv_heads;
+        r.rope_q = r.rope_k = 1;
+        r.Kc = e->sk[l];
+        r.Vc = e->sv[l];
+        r.c_hstride = (long)c.max_audio * D;
+        r.c_bstride = r.c_hstride * c.n_kv_heads;
+        RC(rope_store(r, st));
+        RC(attn_packed(e, M, e->q, tok_row, tok_t, e->sk[l], e->sv[l], c.max_audio, e->kv_len, 1,
+                       c.dec_sliding[l] ? c.sliding_window : 0, e->att, st));
+        RC(linear(e->att, e->q_dim, L.o));
+        RC(resid(L.norms[1], L.norms[2]));
         // --- PM cross attention (q rotated by the decoder progress, :149-165)
-        if (decode) {
-            // cross-q: at the 2b-2b width the register-X GEMV over 2 k-slices of 36 k-steps,
-            // 12 waves (the fused block's Q stage), so a row's sums never depend on the batch
-            int s_q = s_o, rcq = -1;
-            if (M <= 32 && d == 2304 && e->q_dim == 2048) {
-                DecGemmArgs g = dec_args(M, L.cross_q, e->q_dim, d, e->part, e->q_dim, 12);
-                g.X = xn;
-                g.ldx = d;
-                g.splits = 2;
-                g.layout_rx = 1;
-                rcq = gemv_dec(g, EPI_F32, st);
-                if (rcq == 0) s_q = 2;
-                else if (rcq != -1) RC(rcq);
+        RC(gemm(e->xn, d, M, L.cross_q, e->q_dim, d, 1, nullptr, e->q, e->q_dim, EPI_BF16, st, true));
+        r = rope_args();
+        r.X = e->q;
+        r.ldx = e->q_dim;
+        r.nq = c.n_heads;
+        r.rope_q = 1;
+        RC(rope_store(r, st));
+        RC(attn_packed(e, M, e->q, tok_row, tok_t, e->ck[l], e->cv[l], c.max_text, e->enc_len, 0, 0, e->att, st));
+        RC(linear(e->att, e->q_dim, L.cross_o));
+        RC(resid(L.norms[3], L.norms[4]));
+        // --- GeGLU MLP
+        RC(gemm(e->xn, d, M, L.gate_up, 2 * f, d, 1, nullptr, e->act, f, EPI_GEGLU, st, true));
+        RC(linear(e->act, f, L.down));
+        RC(resid(L.norms[5], last ? e->w.dec_final_norm : e->dec[l + 1].norms[0]));
+    }
+    return T5G_OK;
+}
+
+// A decode Linear at one of the plan's sites: on the GEMV when the site has one, on the tiled
+// GEMM (gemm_splits k-slices) otherwise or when the GEMV reports -1 (its per-block LDS does
+// not fit this device's CU count, e.g. a CPX partition). *on_gemv: which of the two ran.
+static int rx_or_gemm(const GemvSite& gv, int gemm_splits, const bf16_t* X, int M, const void* W, int N, int K,
+                      void* Y, int ldy, int epi, hipStream_t st, bool* on_gemv = nullptr) {
+    if (on_gemv) *on_gemv = false;
+    if (gv.nw) {
+        DecGemmArgs g = dec_args(M, W, N, K, Y, ldy, gv.nw);
+        g.X = X;
+        g.ldx = K;
+        g.splits = gv.splits;
+        g.un = gv.un;
+        g.layout_rx = gv.rx;
+        const int rc = gemv_dec(g, epi, st);
+        if (rc != -1) {
+            if (on_gemv) *on_gemv = rc == 0;
+            return rc;
+        }
+    }
+    return gemm(X, K, M, W, N, K, gemm_splits, nullptr, Y, ldy, epi, st);
+}
+
+// One decoder step over the M rows fed by the sampler buffers (tokens, positions, lengths):
+// every Linear writes fp32 split-K slabs into e->part that the next launch sums (spreading
+// the weight streams over >= 512 blocks); decode_plan says which launches a layer runs.
+// Eager checkpoints (softcap > 0) take the same launches: the attention kernels apply the
+// tanh softcap in the score (common.h fast_score).
+static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
+    const t5g_config& c = e->c;
+    const int d = c.hidden, f = c.intermediate;
+    constexpr int s_qkv = t5g_engine::s_qkv, s_o = t5g_engine::s_o, s_down = t5g_engine::s_down;
+    const float* pos = e->next_pos;
+    // one cos/sin table per step: every layer's q/k rotation uses the same positions
+    // (written by layer 0's embedding-norm launch below)
+    const float* tab = e->rope_tab;
+    const DecodePlan p = decode_plan(e, M, e->block_max_rows);
+    // norm after a Linear: h = h + RMSNorm_post(sum of the slabs), xn = RMSNorm_pre(h)
+    auto resid = [&](int splits, const void* post_w, const void* pre_w) -> int {
+        NormArgs n = norm_args(M, d, c.rms_eps);
+        n.part = e->part;
+        n.nsplit = splits;
+        n.ldp = d;
+        n.post_w = (const bf16_t*)post_w;
+        n.resid = e->dh;
+        n.pre_w = (const bf16_t*)pre_w;
+        n.resid_out = e->dh;
+        n.normed_out = e->dxn;
+        return resid_norm(n, st);
+    };
+    // self attention over layer l's cache: q rotated, k rotated + appended inside the launch
+    auto self_attention = [&](int l) -> int {
+        return decode_attention(e, M, e->sk[l], e->sv[l], c.max_audio, e->kv_len, 1,
+                                c.dec_sliding[l] ? c.sliding_window : 0, 0, true, pos, tab, s_qkv, e->qkv_dim, st);
+    };
+    // attention output projection into the norm's slabs
+    auto out_proj = [&](const void* W) -> int {
+        return rx_or_gemm(p.proj, s_o, e->datt, M, W, d, e->q_dim, e->part, d, EPI_F32, st);
+    };
+    NormArgs n0 = embed_norm_args(e, M, e->next_token, e->dh, e->dxn);
+    n0.rope_pos = pos;   // and the step's RoPE table, in the same launch
+    n0.rope_inv_freq = e->w.inv_freq;
+    n0.rope_tab = e->rope_tab;
+    n0.rope_D = c.head_dim;
+    e->s_mode_used = p.tail ? 2 : 0;
+    RC(resid_norm(n0, st));
+    bool qkv_done = false;   // the previous layer's fused block projected this layer's q|k|v
+    for (int l = 0; l < c.n_dec_layers; ++l) {
+        const t5g_layer_weights& L = e->dec[l];
+        const bool last = l == c.n_dec_layers - 1;
+        if (!qkv_done)
+            RC(rx_or_gemm(p.qkv, s_qkv, e->dxn, M, L.qkv, e->qkv_dim, d, e->part, e->qkv_dim, EPI_F32, st));
+        qkv_done = false;
+        FusedMlpArgs fa;
+        if (p.tail) {
+            // layer 0's attention and o-projection as their own launches (the step's
+            // prologue), then every layer's launch runs the next layer's attention and
+            // o-projection at its end (bitwise equal to the launches below)
+            if (l == 0) {
+                RC(self_attention(l));
+                RC(out_proj(L.o));
             }
-            if (rcq != 0) RC(gemm(xn, d, M, L.cross_q, e->q_dim, d, s_o, nullptr, e->part, e->q_dim, EPI_F32, st));
-            RC(decode_attention(e, M, e->ck[l], e->cv[l], c.max_text, e->enc_len, 0, 0, 0, false, pos, tab, s_q,
-                                e->q_dim, st));
-        } else {
-            RC(gemm(xn, d, M, L.cross_q, e->q_dim, d, 1, nullptr, q, e->q_dim, EPI_BF16, st, !decode));
-            RopeArgs r = rope_args();
-            r.X = q;
-            r.ldx = e->q_dim;
-            r.nq = c.n_heads;
-            r.rope_q = 1;
-            RC(rope_store(r, st));
-            RC(attn_packed(e, M, q, tok_row, tok_t, e->ck[l], e->cv[l], c.max_text, e->enc_len, 0, 0, att, st));
+            fa = fused_block_args(e, M, l);
+            if (!fused_block_tail(e, l, fa)) return T5G_EUNSUPPORTED;   // the plan checked every layer
+            RC(fused_mlp(fa, st));
+            ++e->blk_launches;
+            if (!last) ++e->s_launches;
+            qkv_done = true;
+            continue;
         }
-        RC(out_proj(att, L.cross_o));
-        // --- norm + GeGLU MLP: at the 2b-2b width, decode rows <= 32, one persistent launch
-        // (fused.hip; bitwise equal to the three launches below)
-        if (decode && e->fused_mlp && M <= 32 && d == 2304 && f == 9216 && s_o == 4 && s_down == 8 &&
-            c.n_dec_layers >= 2) {
-            const int rc = fused_mlp(fused_args(e, M, l), st);
-            if (rc == 0) {
-                RC(resid(s_down, L.norms[5], last ? e->w.dec_final_norm : e->dec[l + 1].norms[0]));
-                continue;
+        const DecodeLaunch launch = decode_layer_launch(e, p, M, l, fa);
+        // the rest of the layer (o-projection, cross attention, MLP half, the last norm and the
+        // next layer's q|k|v) as one persistent launch (fused.hip fused_block_kernel), with the
+        // attention as its stage S in front or as its own launch before it (all three bitwise
+        // equal to the per-op launches below)
+        if (launch == DL_BLOCK_S || launch == DL_BLOCK) {
+            if (launch == DL_BLOCK) RC(self_attention(l));
+            RC(fused_mlp(fa, st));
+            ++e->blk_launches;
+            if (launch == DL_BLOCK_S) {
+                ++e->s_launches;
+                e->s_mode_used = 1;
             }
-            if (rc != -1) RC(rc);   // -1: a shape / device the launch is not built for
+            qkv_done = !last;
+            continue;
         }
-        RC(resid(s_o, L.norms[3], L.norms[4]));
-        // --- GeGLU MLP (decode: the one-block-per-CU GEMV; register-resident X at the
-        // 2b-2b width, up to 32 rows)
-        if (decode && (M <= 16 || (M <= 32 && d == 2304))) {
-            DecGemmArgs g = dec_args(M, L.gate_up, 2 * f, d, act, f, d == 2304 ? 12 : 8);
-            g.X = xn;
-            g.ldx = d;
-            // register-X at 2b-2b width: every unit's weights requested up front (18.84 ->
-            // 18.39 us at 8 rows, 24.2 -> 23.9 at 32, bitwise equal: tools/probe_rx_all.py)
-            g.un = d == 2304 ? -1 : 8;
-            g.layout_rx = d == 2304;
-            const int rc = gemv_dec(g, EPI_GEGLU, st);
-            if (rc == -1) RC(gemm(xn, d, M, L.gate_up, 2 * f, d, 1, nullptr, act, f, EPI_GEGLU, st, !decode));
-            else RC(rc);
-        } else {
-            RC(gemm(xn, d, M, L.gate_up, 2 * f, d, 1, nullptr, act, f, EPI_GEGLU, st, !decode));
-        }
-        if (decode && M <= 32 && d == 2304 && f == 9216 && s_down == 8) {
-            // down: register-resident X over 36-k-step slices, 32 blocks per slice
-            // (tools/probe_down_rx.py: 11.2 vs 16.3 us at 32 rows, 9.0 vs 9.4 at 8)
-            DecGemmArgs g = dec_args(M, L.down, d, f, e->part, d, 12);
-            g.X = act;
-            g.ldx = f;
-            g.splits = s_down;
-            g.layout_rx = 1;
-            const int rc = gemv_dec(g, EPI_F32, st);
-            if (rc == -1) RC(gemm(act, f, M, L.down, d, f, s_down, nullptr, e->part, d, EPI_F32, st, false));
-            else RC(rc);
-        } else {
-            RC(gemm(act, f, M, L.down, d, f, s_down, nullptr, s_down > 1 ? (void*)e->part : (void*)tmp, d,
-                    s_down > 1 ? EPI_F32 : EPI_BF16, st, !decode));
+        RC(self_attention(l));
+        RC(out_proj(L.o));
+        RC(resid(s_o, L.norms[1], L.norms[2]));
+        // --- PM cross attention (q rotated by the decoder progress, :149-165); the GEMM
+        // fallback of cross-q writes s_o slabs, the GEMV its own two
+        bool q_gemv = false;
+        RC(rx_or_gemm(p.cross_q, s_o, e->dxn, M, L.cross_q, e->q_dim, d, e->part, e->q_dim, EPI_F32, st, &q_gemv));
+        RC(decode_attention(e, M, e->ck[l], e->cv[l], c.max_text, e->enc_len, 0, 0, 0, false, pos, tab,
+                            q_gemv ? p.cross_q.splits : s_o, e->q_dim, st));
+        RC(out_proj(L.cross_o));
+        // --- norm + GeGLU MLP as one persistent launch (fused.hip; bitwise equal to the three
+        // launches below); -1: a shape / device the launch is not built for
+        const int rc = launch == DL_MLP_HALF ? fused_mlp(fa, st) : -1;
+        if (rc != 0) {
+            if (rc != -1) RC(rc);
+            RC(resid(s_o, L.norms[3], L.norms[4]));
+            RC(rx_or_gemm(p.gate_up, 1, e->dxn, M, L.gate_up, 2 * f, d, e->dact, f, EPI_GEGLU, st));
+            RC(rx_or_gemm(p.down, s_down, e->dact, M, L.down, d, f, e->part, d, EPI_F32, st));
         }
         RC(resid(s_down, L.norms[5], last ? e->w.dec_final_norm : e->dec[l + 1].norms[0]));
     }
     return T5G_OK;
 }
 
-static DecGemmArgs dec_args(int M, const void* W, int N, int K, void* Y, int ldy, int nw) {
-    DecGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.M = M;
-    g.K = K;
-    g.W = (const bf16_t*)W;
-    g.N = N;
-    g.NG = ng_pad(N);
-    g.KB = K / 32;
-    g.Y = Y;
-    g.ldy = ldy;
-    g.nw = nw;
-    g.splits = 1;
-    return g;
-}
-
 // one decoder step + predict head for the e->B rows fed by the sampler buffers
 static int head(t5g_engine* e, const bf16_t* xn_rows, int B, hipStream_t st);
 static int head_exact(t5g_engine* e, const bf16_t* xn_rows16, int B, hipStream_t st);
-static int decode_forward(t5g_engine* e, hipStream_t st) {
+int decode_forward(t5g_engine* e, hipStream_t st) {
     if (e->exact) {
         RC(decoder_pass_exact(e, e->B, e->next_token, nullptr, nullptr, e->next_pos, true, st));
         return head_exact(e, e->dxn16, e->B, st);
     }
-    int rc = decoder_pass(e, e->B, e->next_token, nullptr, nullptr, e->next_pos, true, st);
+    int rc = decode_pass(e, e->B, st);
     if (rc) return rc;
     return head(e, e->dxn, e->B, st);
 }
@@ -1561,9 +1437,9 @@ extern "C" int t5g_prefill(t5g_engine* e, int32_t B, int32_t ntok, const int32_t
     HIPCHK(hipMemcpyAsync(e->kv_len, kv_len, B * sizeof(int), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(e->last_rows, last_index, B * sizeof(int), hipMemcpyDeviceToDevice, st));
     int rc = e->exact ? decoder_pass_exact(e, ntok, ids, tok_row, tok_t, pos, false, st)
-                      : decoder_pass(e, ntok, ids, tok_row, tok_t, pos, false, st);
+                      : prefill_pass(e, ntok, ids, tok_row, tok_t, pos, st);
     if (rc) return rc;
-    // the last decoder_pass norm wrote final-normed hidden of every token into xn;
+    // the pass's last norm wrote final-normed hidden of every token into xn;
     // gather each row's last token
     NormArgs n = norm_args(B, c.hidden, c.rms_eps);
     // copy rows: reuse resid_norm as a gather (delta = xn, no norms)
@@ -1619,23 +1495,6 @@ extern "C" int t5g_engine_set_noise_mt(t5g_engine* e, const uint32_t* raw, int32
     if (e->noise_mt != raw || e->noise_mt_steps != steps) drop_graphs(e);   // baked into the captured graphs
     e->noise_mt = raw;
     e->noise_mt_steps = steps;
-    return T5G_OK;
-}
-
-extern "C" int t5g_mt_stream(const uint32_t* init, int32_t B, int64_t n_out, int64_t out_stride, uint32_t* out,
-                             int64_t snap_every, int32_t n_snap, uint32_t* snap, void* stream) {
-    RC(mt_stream(init, B, (long)n_out, (long)out_stride, out, (long)snap_every, n_snap, snap, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_sdpa_expf(const float* x, float* y, int64_t n, void* stream) {
-    if (n < 0 || (n > 0 && (!x || !y))) return T5G_EINVAL;
-    RC(sdpa_expf_array(x, y, (long)n, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_mt_exponential(const uint32_t* raw, int64_t n, void* q, void* stream) {
-    RC(mt_exponential(raw, (long)n, (bf16_t*)q, (hipStream_t)stream));
     return T5G_OK;
 }
 
@@ -1701,26 +1560,17 @@ extern "C" int t5g_decode(t5g_engine* e, int32_t n_steps, int32_t use_graph, voi
     }
     if (!e->gexec || e->graph_B != e->B) {
         drop_graphs(e);
-        if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
         for (int which = 0; which < 2; ++which) {
-            HIPCHK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-            int rc = T5G_OK;
-            for (int i = 0; i < (which ? GRAPH_STEPS : 1) && !rc; ++i) rc = decode_iter(e, e->cap_stream);
-            hipGraph_t g = nullptr;
-            hipError_t ec = hipStreamEndCapture(e->cap_stream, &g);
-            if (rc || ec != hipSuccess) {
-                if (g) hipGraphDestroy(g);
-                drop_graphs(e);
-                return rc ? rc : T5G_EHIP;
+            auto iters = [&](hipStream_t cs) {
+                int rc = T5G_OK;
+                for (int i = 0; i < (which ? GRAPH_STEPS : 1) && !rc; ++i) rc = decode_iter(e, cs);
+                return rc;
+            };
+            const int rc = capture(e, iters, which ? &e->graph_n : &e->graph, which ? &e->gexec_n : &e->gexec);
+            if (rc) {
+                drop_graphs(e);   // never a one-step graph without its GRAPH_STEPS twin
+                return rc;
             }
-            hipGraphExec_t x = nullptr;
-            if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
-                hipGraphDestroy(g);
-                drop_graphs(e);
-                return T5G_EHIP;
-            }
-            (which ? e->graph_n : e->graph) = g;
-            (which ? e->gexec_n : e->gexec) = x;
         }
         e->graph_B = e->B;
     }
@@ -1740,7 +1590,7 @@ extern "C" int t5g_read_state(t5g_engine* e, t5g_sampler_state* out, int32_t B, 
 
 // The fused launches' sticky timeout word: non-zero when an in-launch hand-off gave up
 // (outputs of those launches invalid). Cleared with the counters; T5G_EHANDOFF then.
-static int check_handoff(t5g_engine* e, hipStream_t st) {
+int check_handoff(t5g_engine* e, hipStream_t st) {
     unsigned tmo = 0;
     HIPCHK(hipMemcpyAsync(&tmo, e->fsync, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1881,22 +1731,8 @@ extern "C" int t5g_step_only(t5g_engine* e, void* stream) {
         if (e->graph_fwd) hipGraphDestroy(e->graph_fwd);
         e->gexec_fwd = nullptr;
         e->graph_fwd = nullptr;
-        if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
-        HIPCHK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int rc = decode_forward(e, e->cap_stream);
-        hipGraph_t g = nullptr;
-        const hipError_t ec = hipStreamEndCapture(e->cap_stream, &g);
-        if (rc || ec != hipSuccess) {
-            if (g) hipGraphDestroy(g);
-            return rc ? rc : T5G_EHIP;
-        }
-        hipGraphExec_t x = nullptr;
-        if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
-            hipGraphDestroy(g);
-            return T5G_EHIP;
-        }
-        e->graph_fwd = g;
-        e->gexec_fwd = x;
+        const int rc = capture(e, [&](hipStream_t cs) { return decode_forward(e, cs); }, &e->graph_fwd, &e->gexec_fwd);
+        if (rc) return rc;   // the fast path's graphs stay
         e->graph_fwd_B = e->B;
     }
     HIPCHK(hipGraphLaunch(e->gexec_fwd, st));
@@ -1941,12 +1777,6 @@ extern "C" int t5g_engine_set_rope_exc(t5g_engine* e, const uint32_t* tab, int32
     return T5G_OK;
 }
 
-extern "C" int t5g_sort_emu_wave(int32_t n, int32_t S, int32_t* pos_dev, float* val_dev, int32_t* tag_dev,
-                                 int32_t* fail_dev, void* stream) {
-    RC(sort_emu_wave(n, S, pos_dev, val_dev, tag_dev, fail_dev, (hipStream_t)stream));
-    return T5G_OK;
-}
-
 extern "C" void* t5g_engine_cache_ptr(t5g_engine* e, int32_t layer, int32_t which, int64_t* head_stride,
                                       int64_t* row_stride) {
     if (!e || layer < 0 || layer >= e->c.n_dec_layers || which < 0 || which > 3) return nullptr;
@@ -1966,596 +1796,5 @@ extern "C" int t5g_copy_logits(t5g_engine* e, void* dst, int32_t B, void* stream
 extern "C" int t5g_sample_only(t5g_engine* e, int32_t B, const void* logits, int32_t ld, void* stream) {
     if (!e || B <= 0 || B > e->c.max_batch) return T5G_EINVAL;
     RC(sample(sampler_args(e, (const bf16_t*)logits, ld, B), (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_gemm(const void* X, int32_t ldx, int32_t M, const void* Wp, int32_t N, int32_t K, int32_t splits,
-                        const void* bias, void* Y, int32_t ldy, int32_t epi, void* stream) {
-    if (!X || !Wp || !Y || M <= 0 || N <= 0 || K % 32) return T5G_EINVAL;
-    const bool prefill = (epi & T5G_GEMM_PREFILL) != 0, pf_reg = (epi & T5G_GEMM_PREFILL_REG) != 0;
-    RC(gemm((const bf16_t*)X, ldx, M, Wp, N, K, splits, bias, Y, ldy, epi & 0xff, (hipStream_t)stream, prefill,
-            pf_reg));
-    return T5G_OK;
-}
-
-extern "C" int t5g_time_gemm(const void* X, int32_t ldx, int32_t M, const void* const* Wp_list, int32_t n_w,
-                             int32_t N, int32_t K, int32_t splits, void* Y, int32_t ldy, int32_t epi, int32_t iters,
-                             void* stream, float* avg_us) {
-    if (iters <= 0 || !avg_us || !Wp_list || n_w <= 0) return T5G_EINVAL;
-    for (int i = 0; i < n_w; ++i)
-        if (!Wp_list[i]) return T5G_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    const bool pf = (epi & T5G_GEMM_PREFILL) != 0, pf_reg = (epi & T5G_GEMM_PREFILL_REG) != 0;
-    epi &= 0xff;
-    RC(gemm((const bf16_t*)X, ldx, M, Wp_list[0], N, K, splits, nullptr, Y, ldy, epi, st, pf, pf_reg));  // warm
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i)
-        RC(gemm((const bf16_t*)X, ldx, M, Wp_list[i % n_w], N, K, splits, nullptr, Y, ldy, epi, st, pf, pf_reg));
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / iters;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return T5G_OK;
-}
-
-extern "C" int t5g_time_decode_step(t5g_engine* e, int32_t iters, void* stream, float* avg_us) {
-    if (!e || iters <= 0 || !avg_us || e->B <= 0) return T5G_EINVAL;
-    e->decode_state_invalid = true;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) {
-        int rc = decode_forward(e, st);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / iters;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return check_handoff(e, st);
-}
-
-// hipEvent-timed exact decode Linears (parity mode's dominant kernel, xmm_dec_kernel): per
-// iteration the six launches of one decoder layer as the parity decode step runs them --
-// q|k|v, o, cross-q, cross-o (bf16 out), gate/up (GeGLU epilogue), down (K parts) -- on
-// the decode X16 buffers of B rows, layers rotated so every launch streams from HBM.
-// Average microseconds per layer (six launches) in *avg_us.
-extern "C" int t5g_time_exact_linears(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
-    if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || !e->exact || !e->xmm_ready) return T5G_EINVAL;
-    e->decode_state_invalid = true;
-    const t5g_config& c = e->c;
-    const int d = c.hidden, f = c.intermediate;
-    hipStream_t st = (hipStream_t)stream;
-    auto layer = [&](int l) -> int {
-        const t5g_engine::XLayer& X = e->dec_x[l];
-        RC(xlin16(e, e->dxn16, B, X.qkv, e->qkv_dim, d, nullptr, e->qkv, e->qkv_dim, nullptr, EPI_BF16, nullptr,
-                  nullptr, e->q_dim, e->kv_dim, e->q_dim, st));
-        RC(xlin16(e, e->datt16, B, X.o, d, e->q_dim, nullptr, e->tmp, d, nullptr, EPI_BF16, nullptr, nullptr, d, 0, 0,
-                  st));
-        RC(xlin16(e, e->dxn16, B, X.cross_q, e->q_dim, d, nullptr, e->dq, e->q_dim, nullptr, EPI_BF16, nullptr,
-                  nullptr, e->q_dim, 0, 0, st));
-        RC(xlin16(e, e->datt16, B, X.cross_o, d, e->q_dim, nullptr, e->tmp, d, nullptr, EPI_BF16, nullptr, nullptr, d,
-                  0, 0, st));
-        RC(xlin16(e, e->dxn16, B, X.gate_up, 2 * f, d, nullptr, nullptr, f, e->dact16, EPI_GEGLU, nullptr, nullptr, f,
-                  0, 0, st));
-        int np = 0;
-        RC(xlin16_dec_parts(e, e->dact16, B, X.down, d, f, e->tmp, d, nullptr, &np, st));
-        return T5G_OK;
-    };
-    RC(layer(0));   // untimed: the first launch's one-time setup
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) RC(layer(i % c.n_dec_layers));
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / iters;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return T5G_OK;
-}
-
-// hipEvent-timed parity-mode persistent layer launches (xlayer.hip; bench.py parity roofline):
-// whole rotations over the layers as a decode step runs them (layer l's counter set zeroed by
-// layer l - 1's launch), one untimed rotation first, on the engine's current decode state
-extern "C" int t5g_time_xlayer(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
-    if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || !e->exact || !e->xmm_ready) return T5G_EINVAL;
-    if (!xlayer_usable(e, B)) return T5G_EUNSUPPORTED;
-    e->decode_state_invalid = true;
-    hipStream_t st = (hipStream_t)stream;
-    const int L = e->c.n_dec_layers;
-    const int n = (iters + L - 1) / L * L;
-    for (int l = 0; l < L; ++l) {
-        const int rc = xlayer_launch(xlayer_args(e, B, l), st);
-        if (rc) return rc == -1 ? T5G_EUNSUPPORTED : T5G_EHIP;
-    }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
-    int rc = 0;
-    // diagnostic T5G_TIME_SHARE: "chain" -- every launch reads layer 1's o / cross q / cross o /
-    // q|k|v weights and cross K / V (its G / D weights rotate); "gd" -- layer 1's gate/up and
-    // down (the rest rotates): which bytes' cache residency the launch is sensitive to
-    const char* share_s = getenv("T5G_TIME_SHARE");
-    const int share = !share_s ? 0 : !strcmp(share_s, "chain") ? 1 : !strcmp(share_s, "gd") ? 2 : 0;
-    const XLayerArgs a1 = xlayer_args(e, B, 1);
-    for (int i = 0; i < n && !rc; ++i) {
-        XLayerArgs a = xlayer_args(e, B, i % L);
-        if (share == 1 && a.Wqkv) {
-            a.Wo = a1.Wo, a.Wq = a1.Wq, a.Wco = a1.Wco, a.Wqkv = a1.Wqkv, a.ck = a1.ck, a.cv = a1.cv;
-        } else if (share == 2) {
-            a.Wgu = a1.Wgu, a.Wd = a1.Wd;
-        }
-        rc = xlayer_launch(a, st);
-    }
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (rc) return rc == -1 ? T5G_EUNSUPPORTED : T5G_EHIP;
-    *avg_us = ms * 1000.f / (float)n;
-    return check_handoff(e, st);
-}
-
-// hipEvent-timed fused decode-MLP launches (bench.py roofline leg): layers rotated, so every
-// launch streams its weights from HBM (2.2 GB of gate/up + down > the 256 MiB Infinity Cache)
-extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
-    if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
-    e->decode_state_invalid = true;
-    hipStream_t st = (hipStream_t)stream;
-    const int L = e->c.n_dec_layers;
-    // whole rotations over the layers, as a decode step runs them: layer l's launch finds
-    // its counter set zeroed by layer l - 1's (the last launch before this call was a step's
-    // last layer, which zeroed layer 0's set); one untimed rotation first
-    const int n = (iters + L - 1) / L * L;
-    // the launch decoder_pass runs at B rows: the cross-attention chain + MLP block up to
-    // 16 rows when the device supports it, the MLP half alone otherwise
-    const bool block = B <= 16 && fused_mlp_check(fused_block_args(e, B, 0)) == 0;
-    auto args = [&](int l) { return block ? fused_block_args(e, B, l) : fused_args(e, B, l); };
-    int rc = T5G_OK;
-    for (int l = 0; l < L && !rc; ++l) rc = fused_mlp(args(l), st);
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < n && !rc; ++i) rc = fused_mlp(args(i % L), st);
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (rc) return rc == -1 ? T5G_EUNSUPPORTED : T5G_EHIP;
-    *avg_us = ms * 1000.f / (float)n;
-    return check_handoff(e, st);   // a timed launch that gave up would report a false rate
-}
-
-// hipEvent-timed persistent layer launches WITH the self-attention stage S, as the fast
-// decode step runs them (bench.py roofline leg): whole rotations over the layers at the
-// cache lengths the last call left (each launch re-appends its rows' last key and value, the
-// values the slabs in e->part give). *keys = the keys one launch reads per kv head, summed
-// over the rows and averaged over the layers (sliding layers clipped to their window).
-extern "C" int t5g_time_decode_layer(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us,
-                                     float* keys) {
-    if (!e || iters <= 0 || !avg_us || !keys || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
-    e->decode_state_invalid = true;
-    hipStream_t st = (hipStream_t)stream;
-    const t5g_config& c = e->c;
-    const int L = c.n_dec_layers;
-    // attn_in_block 1: launch l runs layer l's attention in front; 2: layer l + 1's at its end
-    // (the last launch none; layer 0's is the step's own launch, not timed here)
-    // (mode 2 on a call the tail does not take runs S in front, as decoder_pass does)
-    // (the hook times the one-tile launch: past 16 rows bench.py prices the MLP-half launch)
-    if (B > 16) return T5G_EUNSUPPORTED;
-    bool tail = e->attn_in_block == 2;
-    FusedMlpArgs fa;
-    for (int l = 0; l < L && tail; ++l) {
-        fa = fused_block_args(e, B, l);
-        tail = fused_block_tail(e, B, l, fa);
-    }
-    auto args = [&](int l, FusedMlpArgs& fa) {
-        fa = fused_block_args(e, B, l);
-        if (tail) return fused_block_tail(e, B, l, fa);
-        return fused_mlp_check(fa) == 0 && fused_block_self(e, B, l, fa);
-    };
-    for (int l = 0; l < L; ++l)
-        if (!args(l, fa)) return T5G_EUNSUPPORTED;
-    std::vector<int> len(B);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(len.data(), e->kv_len, sizeof(int) * B, hipMemcpyDeviceToHost));
-    double ksum = 0.0;
-    for (int l = tail ? 1 : 0; l < L; ++l)
-        for (int b = 0; b < B; ++b) {
-            const int w = c.dec_sliding[l] ? c.sliding_window : 0;
-            ksum += w > 0 ? std::min(len[b], w) : len[b];
-        }
-    *keys = (float)(ksum / L);
-    const int n = (iters + L - 1) / L * L;
-    // diagnostic T5G_TIME_SHARE (tools/probe_cache_share.py): "chain" -- every launch reads
-    // layer 1's cross q / cross o / next q|k|v / next o weights and cross K / V (they then stay
-    // in the Infinity Cache; the G / D weights rotate); "gd" -- layer 1's gate/up and down.
-    // Each launch keeps its own layer's hand-off counter sets, so the synchronisation is the
-    // decode step's (a launch repeating a layer would find its counters un-zeroed)
-    const char* share_s = getenv("T5G_TIME_SHARE");
-    const int share = !share_s ? 0 : !strcmp(share_s, "chain") ? 1 : !strcmp(share_s, "gd") ? 2 : 0;
-    FusedMlpArgs f1;
-    if (share && !args(1, f1)) return T5G_EUNSUPPORTED;
-    int rc = 0;
-    for (int l = 0; l < L && !rc; ++l) rc = args(l, fa) ? fused_mlp(fa, st) : -1;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < n && !rc; ++i) {
-        if (!args(i % L, fa)) {
-            rc = -1;
-            break;
-        }
-        if (share == 1 && i % L != L - 1) {
-            fa.Wq = f1.Wq, fa.Wo = f1.Wo, fa.Wqkv = f1.Wqkv, fa.ck = f1.ck, fa.cv = f1.cv;
-            if (fa.Wo1n) fa.Wo1n = f1.Wo1n;
-        } else if (share == 2) {
-            fa.Wgu = f1.Wgu, fa.Wd = f1.Wd;
-        }
-        rc = fused_mlp(fa, st);
-    }
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (rc) return rc == -1 ? T5G_EUNSUPPORTED : T5G_EHIP;
-    *avg_us = ms * 1000.f / (float)n;
-    return check_handoff(e, st);
-}
-
-// work = scores | chunk maxima (fp32)
-// work of t5g_attention_decode(_flash), in 4-byte words: scores | chunk maxima | flash
-// partials | flash chunk stats | flash tickets (last, so one zeroing covers them)
-struct AttnWork {
-    int64_t sc, mx, fp, fs, tk;
-};
-static AttnWork attn_work_layout(int B, int Hq, int Hkv, int D, int cap) {
-    const int64_t nsplit = (cap + 63) / 64, G = Hq / Hkv;
-    AttnWork w;
-    w.sc = (int64_t)B * Hq * cap;
-    w.mx = (int64_t)B * Hkv * nsplit * G;
-    w.fp = (int64_t)B * Hkv * nsplit * G * D;
-    w.fs = (int64_t)B * Hkv * nsplit * G * 2;
-    w.tk = (int64_t)B * Hkv;
-    return w;
-}
-
-extern "C" int64_t t5g_attention_decode_work_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t D, int32_t cap) {
-    if (B <= 0 || Hkv <= 0 || Hq % Hkv || D <= 0 || cap <= 0) return -1;
-    const AttnWork w = attn_work_layout(B, Hq, Hkv, D, cap);
-    return (w.sc + w.mx + w.fp + w.fs + w.tk) * 4;
-}
-
-static int attention_decode_abi(const t5g_attn_decode_args* g, bool flash, void* stream);
-extern "C" int t5g_attention_decode(const t5g_attn_decode_args* g, void* stream) {
-    return attention_decode_abi(g, false, stream);
-}
-extern "C" int t5g_attention_decode_flash(const t5g_attn_decode_args* g, void* stream) {
-    return attention_decode_abi(g, true, stream);
-}
-
-static int attention_decode_abi(const t5g_attn_decode_args* g, bool flash, void* stream) {
-    if (!g || !g->q || !g->k_cache || !g->v_cache || !g->kv_len || !g->out || !g->work) return T5G_EINVAL;
-    if (g->B <= 0 || g->n_kv_heads <= 0 || g->n_heads % g->n_kv_heads || g->cap <= 0 ||
-        g->cap > SDPA_KV_BLOCK * SDPA_MAX_BLOCKS)
-        return T5G_EINVAL;
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Q = (const bf16_t*)g->q;
-    a.ldq = g->n_heads * g->head_dim;
-    a.Mq = g->B;
-    a.K = (const bf16_t*)g->k_cache;
-    a.V = (const bf16_t*)g->v_cache;
-    a.kv_hstride = (long)g->cap * g->head_dim;
-    a.kv_bstride = a.kv_hstride * g->n_kv_heads;
-    a.kv_len = g->kv_len;
-    a.Hkv = g->n_kv_heads;
-    a.D = g->head_dim;
-    a.G = g->n_heads / g->n_kv_heads;
-    a.causal = g->causal;
-    a.window = g->window;
-    a.scale = g->scale;
-    a.O = (bf16_t*)g->out;
-    a.ldo = a.ldq;
-    a.chunk = 64;
-    a.nsplit = (g->cap + 63) / 64;
-    a.kv_cap = g->cap;
-    const AttnWork w = attn_work_layout(g->B, g->n_heads, g->n_kv_heads, g->head_dim, g->cap);
-    a.sbuf = (float*)g->work;
-    a.mbuf = a.sbuf + w.sc;
-    a.flash = flash ? 1 : 0;
-    a.fpart = a.mbuf + w.mx;
-    a.fstat = a.fpart + w.fp;
-    a.fticket = (unsigned*)(a.fstat + w.fs);
-    RC(attention_decode(a, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_resid_norm(int32_t M, int32_t d, const void* delta, const void* resid, const void* post_w,
-                              const void* pre_w, float eps, void* resid_out, void* normed_out, void* stream) {
-    if (M <= 0 || d <= 0 || d % 8 || !delta || !resid_out) return T5G_EINVAL;
-    NormArgs n = norm_args(M, d, eps);
-    n.delta = (const bf16_t*)delta;
-    n.resid = (const bf16_t*)resid;
-    n.post_w = (const bf16_t*)post_w;
-    n.pre_w = (const bf16_t*)pre_w;
-    n.resid_out = (bf16_t*)resid_out;
-    n.normed_out = (bf16_t*)normed_out;
-    RC(resid_norm(n, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-static_assert(sizeof(t5g_gemv_args) == 152, "t5g_gemv_args layout");
-
-static int gemv_from_abi(const t5g_gemv_args* g, const void* W, DecGemmArgs* out) {
-    if (!g || !W || !g->Y || g->M <= 0 || g->N <= 0 || g->K <= 0 || g->K % 32) return T5G_EINVAL;
-    if (g->pro != 0 || g->layout < 0 || g->layout > 1) return T5G_EUNSUPPORTED;   // prologue variants were removed
-    DecGemmArgs a = dec_args(g->M, W, g->N, g->K, g->Y, g->ldy, g->nw);
-    a.X = (const bf16_t*)g->X;
-    a.ldx = g->ldx;
-    a.bias = (const bf16_t*)g->bias;
-    a.un = g->un;
-    a.max_grid = g->max_grid;
-    a.splits = g->splits > 1 ? g->splits : 1;
-    a.layout_rx = g->layout == 1;
-    *out = a;
-    return T5G_OK;
-}
-
-extern "C" int t5g_gemv(const t5g_gemv_args* g, void* stream) {
-    DecGemmArgs a;
-    int rc = gemv_from_abi(g, g ? g->W : nullptr, &a);
-    if (rc) return rc;
-    RC(gemv_dec(a, g->epi, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_time_gemv(const t5g_gemv_args* g, const void* const* Wp_list, int32_t n_w, int32_t iters,
-                             void* stream, float* avg_us) {
-    if (!g || !Wp_list || n_w <= 0 || iters <= 0 || !avg_us) return T5G_EINVAL;
-    std::vector<DecGemmArgs> as((size_t)n_w);
-    for (int i = 0; i < n_w; ++i) {
-        int rc = gemv_from_abi(g, Wp_list[i], &as[i]);
-        if (rc) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    RC(gemv_dec(as[0], g->epi, st));  // warm
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) RC(gemv_dec(as[i % n_w], g->epi, st));
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / iters;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return T5G_OK;
-}
-
-extern "C" int t5g_exact_linear(const void* X, int32_t ldx, int32_t M, const void* Wp, int32_t N, int32_t K,
-                                int32_t kb32, const void* bias, const void* gelu_lut, void* Y, int32_t ldy, int32_t epi,
-                                void* stream) {
-    if (!X || !Wp || !Y || M <= 0 || N <= 0 || K <= 0 || K % 32 || kb32 < 0) return T5G_EINVAL;
-    ExactLinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.X = (const bf16_t*)X;
-    a.ldx = ldx;
-    a.M = M;
-    a.W = (const bf16_t*)Wp;
-    a.N = N;
-    a.NG = ng_pad(N);
-    a.KB = K / 32;
-    a.bias = (const bf16_t*)bias;
-    a.Y = Y;
-    a.ldy = ldy;
-    a.kb_fixed = kb32;
-    a.gelu_lut = (const uint16_t*)gelu_lut;
-    RC(exact_linear(a, epi, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_pack_e16(const void* p16, void* e16, int64_t bytes, void* stream) {
-    RC(pack_e16((const bf16_t*)p16, (bf16_t*)e16, (long)bytes, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-extern "C" int t5g_to_x16(const void* X, int32_t ldx, int32_t M, int32_t K, void* Y16, void* stream) {
-    RC(to_x16((const bf16_t*)X, ldx, M, K, (bf16_t*)Y16, (hipStream_t)stream));
-    return T5G_OK;
-}
-
-// hipEvent-timed xmm launches on E16 weights W16_list[i % n_w] (rotate past the Infinity
-// Cache so every launch streams from HBM, as inside a decode step); epi | 0x1000: also the
-// X16 output (Y16 = Y) instead of row-major
-extern "C" int t5g_time_xmm(const void* X16, int32_t M, const void* const* W16_list, int32_t n_w, int32_t N,
-                            int32_t K, int32_t epi, const void* bias, void* Y, int32_t ldy, int32_t iters,
-                            void* stream, float* avg_us) {
-    if (!X16 || !W16_list || n_w <= 0 || !Y || iters <= 0 || !avg_us || K % 32) return T5G_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    XmmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.X16 = (const bf16_t*)X16;
-    a.M = M;
-    a.N = N;
-    a.NG = ng_pad(N);
-    a.KB = K / 32;
-    a.bias = (const bf16_t*)bias;
-    if (epi & 0x1000) a.Y16 = (bf16_t*)Y;
-    else a.Y = Y;
-    a.ldy = ldy;
-    a.timing_var = (epi & 0x4000) ? 1 : ((epi & 0x8000) ? 2 : 0);   // decode-kernel timing variants
-    epi &= 0xff;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    a.W = (const bf16_t*)W16_list[0];
-    RC(xmm(a, epi, st));
-    HIPCHK(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) {
-        a.W = (const bf16_t*)W16_list[i % n_w];
-        RC(xmm(a, epi, st));
-    }
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / iters;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return T5G_OK;
-}
-
-// The same Linear on the f32-MFMA kernels (xmm.hip): X converted to X16 and the packed W
-// to E16 in temporaries (test / probe entry point; the engine keeps both resident)
-extern "C" int t5g_xmm_linear(const void* X, int32_t ldx, int32_t M, const void* Wp, int32_t N, int32_t K,
-                              int32_t kb32, const void* bias, const void* gelu_lut, void* Y, int32_t ldy, int32_t epi,
-                              void* stream) {
-    if (!X || !Wp || !Y || M <= 0 || N <= 0 || K <= 0 || K % 32 || kb32 < 0) return T5G_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const long wbytes = (long)ng_pad(N) * 16 * K * 2;
-    const long xbytes = (long)((M + 15) / 16) * 16 * K * 2;
-    bf16_t *w16 = nullptr, *x16 = nullptr;
-    HIPCHK(hipMallocAsync((void**)&w16, (size_t)wbytes, st));
-    HIPCHK(hipMallocAsync((void**)&x16, (size_t)xbytes, st));
-    int rc = pack_e16((const bf16_t*)Wp, w16, wbytes, st);
-    if (!rc) rc = to_x16((const bf16_t*)X, ldx, M, K, x16, st);
-    if (!rc) {
-        XmmArgs a;
-        memset(&a, 0, sizeof(a));
-        a.X16 = x16;
-        a.M = M;
-        a.W = w16;
-        a.N = N;
-        a.NG = ng_pad(N);
-        a.KB = K / 32;
-        a.bias = (const bf16_t*)bias;
-        if (epi & 0x2000) {   // K parts of kb32 chunks: Y = fp32 part values [parts][M][N]
-            a.part_out = (float*)Y;
-            a.part_kbc = kb32;
-        } else {
-            a.Y = Y;
-            a.ldy = ldy;
-            a.kb_fixed = kb32;
-        }
-        a.gelu_lut = (const uint16_t*)gelu_lut;
-        rc = xmm(a, epi & 0xff, st);
-    }
-    hipFreeAsync(w16, st);
-    hipFreeAsync(x16, st);
-    RC(rc);
-    return T5G_OK;
-}
-
-extern "C" int t5g_eager_attention(const void* q, int32_t Mq, const int32_t* q_row, const int32_t* q_pos,
-                                   const int32_t* q_len, const void* k_cache, const void* v_cache, int32_t cap,
-                                   const int32_t* kv_len, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
-                                   int32_t causal, int32_t window, float scale, float softcap,
-                                   const uint16_t* tanh_lut, void* out, void* stream) {
-    if (!q || !k_cache || !v_cache || !kv_len || !out || !tanh_lut || Mq <= 0 || cap <= 0 || n_kv_heads <= 0 ||
-        n_heads % n_kv_heads || head_dim <= 0)
-        return T5G_EINVAL;
-    ExactAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Q = (const bf16_t*)q;
-    a.ldq = n_heads * head_dim;
-    a.Mq = Mq;
-    a.q_row = q_row;
-    a.q_pos = q_pos;
-    a.q_len = q_len;
-    a.K = (const bf16_t*)k_cache;
-    a.V = (const bf16_t*)v_cache;
-    a.kv_hstride = (long)cap * head_dim;
-    a.kv_bstride = a.kv_hstride * n_kv_heads;
-    a.kv_len = kv_len;
-    a.Hq = n_heads;
-    a.Hkv = n_kv_heads;
-    a.D = head_dim;
-    a.causal = causal;
-    a.window = window;
-    a.scale = scale;
-    a.softcap = softcap;
-    a.tanh_lut = tanh_lut;
-    a.O = (bf16_t*)out;
-    a.ldo = a.ldq;
-    hipStream_t st = (hipStream_t)stream;
-    float* sb = nullptr;
-    HIPCHK(hipMallocAsync((void**)&sb, (size_t)Mq * n_heads * cap * 4, st));
-    const int rc = eager_attention(a, sb, cap, st);
-    hipFreeAsync(sb, st);
-    if (rc == -3) return T5G_EUNSUPPORTED;
-    RC(rc);
-    return T5G_OK;
-}
-
-extern "C" int t5g_exact_attention(const void* q, int32_t Mq, const int32_t* q_row, const int32_t* q_pos,
-                                   const int32_t* q_len, const void* k_cache, const void* v_cache, int32_t cap,
-                                   const int32_t* kv_len, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
-                                   int32_t causal, int32_t window, float scale, int32_t threads, void* out,
-                                   void* stream) {
-    if (!q || !k_cache || !v_cache || !kv_len || !out || Mq <= 0 || cap <= 0 || n_kv_heads <= 0 ||
-        n_heads % n_kv_heads || head_dim <= 0 || threads <= 0)
-        return T5G_EINVAL;
-    ExactAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Q = (const bf16_t*)q;
-    a.ldq = n_heads * head_dim;
-    a.Mq = Mq;
-    a.q_row = q_row;
-    a.q_pos = q_pos;
-    a.q_len = q_len;
-    a.K = (const bf16_t*)k_cache;
-    a.V = (const bf16_t*)v_cache;
-    a.kv_hstride = (long)cap * head_dim;
-    a.kv_bstride = a.kv_hstride * n_kv_heads;
-    a.kv_len = kv_len;
-    a.Hq = n_heads;
-    a.Hkv = n_kv_heads;
-    a.D = head_dim;
-    a.causal = causal;
-    a.window = window;
-    a.scale = scale;
-    a.threads = threads;
-    a.O = (bf16_t*)out;
-    a.ldo = a.ldq;
-    if (!q_pos && !q_len) {   // one query per row at its last key: the engine's decode launches (xattn.hip)
-        hipStream_t st = (hipStream_t)stream;
-        const int G = n_heads / n_kv_heads, nsplit = (cap + 63) / 64;
-        float *sb = nullptr, *mb = nullptr;
-        HIPCHK(hipMallocAsync((void**)&sb, (size_t)Mq * n_heads * cap * 4, st));
-        HIPCHK(hipMallocAsync((void**)&mb, (size_t)Mq * n_kv_heads * nsplit * G * 4, st));
-        const int rc = exact_attention_decode(a, sb, mb, cap, st);
-        hipFreeAsync(sb, st);
-        hipFreeAsync(mb, st);
-        RC(rc);
-        return T5G_OK;
-    }
-    RC(exact_attention(a, (hipStream_t)stream));
     return T5G_OK;
 }

@@ -1,5 +1,5 @@
 // Block-level timeline of one T5Gemma 2b-2b decoder layer at batch 8 (decode step), the
-// same kernel chain the engine captures (engine.hip decoder_pass), run on the diagnostic
+// same kernel chain the engine captures (engine.hip decode_pass), run on the diagnostic
 // library variant (build.py --dbg: every block of the instrumented kernels records the
 // 100 MHz device clock at numbered points, common.h T5G_TS). For the third of four layers
 // (distinct weights per layer, HBM-cold like inside a 26-layer step) it prints, per
