@@ -156,7 +156,12 @@ int t5g_prefill(t5g_engine* e, int32_t B, int32_t ntok, const int32_t* ids_dev, 
 /* Sampler setup (host arrays, copied): rows[B], init state[B], shared top-k list
  * and silence-token buffers. noise_dev: NULL for on-device Philox noise, else
  * bf16 [B][noise_steps][n_audio_tokens] -- the exact exponential draws of
- * torch.multinomial (parity mode). */
+ * torch.multinomial (parity mode).
+ * Checked before anything is copied (T5G_EINVAL): every row's
+ * [silence_off, silence_off + n_silence) and [top_k_list_off, top_k_list_off +
+ * top_k_list_len) lie inside the uploaded lists, no offset or length is negative, and
+ * init[b].prev_token < n_audio_tokens (the kernels index the lists and the logits with
+ * them unchecked). */
 int t5g_sampler_setup(t5g_engine* e, int32_t B, const t5g_sampler_row* rows, const t5g_sampler_state* init,
                       const int32_t* top_k_list, int32_t n_top_k_list, const int32_t* silence, int32_t n_silence,
                       const void* noise_dev, int32_t noise_steps, void* stream);

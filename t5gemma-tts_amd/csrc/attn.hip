@@ -1093,6 +1093,11 @@ __global__ __launch_bounds__(256) void attn_pvc_kernel(AttnArgs a) {
 template <int D, int G>
 static int launch_decode(const AttnArgs& a_in, hipStream_t st) {
     AttnArgs a = a_in;
+    // the flash form's buffers and thread budget, per built geometry: a geometry no kernel is
+    // built for never gets here and is reported as unsupported, not as a bad argument
+    if (a.flash && a.nsplit > 1 && (!a.fpart || !a.fstat || !a.fticket || G * D / 4 > 256 - 64 * G ||
+                                    (long)a.Mq * a.Hkv * a.nsplit * G * D * 4 > 0x7fff0000L))
+        return -1;
     a.head_split = 1;
     if constexpr (G == 2) {
         // one chunk and nothing appended (cross attention): one workgroup per q head
@@ -1134,9 +1139,6 @@ int attention_decode(const AttnArgs& a, hipStream_t st) {
     // row, <= the cache capacity: rows longer than nsplit * 64 keys are refused on the host)
     if (a.nsplit < 1 || a.nsplit > (a.kv_cap + DCH - 1) / DCH) return -1;
     if (a.nsplit > 1 && (!a.sbuf || !a.mbuf || a.nsplit > DEC_MAX_CHUNKS)) return -1;
-    if (a.flash && a.nsplit > 1 && (!a.fpart || !a.fstat || !a.fticket || a.G * a.D / 4 > 256 - 64 * a.G ||
-                                    (long)a.Mq * a.Hkv * a.nsplit * a.G * a.D * 4 > 0x7fff0000L))
-        return -1;
     if (a.append && (!a.Qpart || !a.rope_tab || (a.G + 2) * a.D / 4 > 256)) return -1;
     if (a.Qpart && (a.q_nsplit < 1 || a.q_nsplit > QSMAX)) return -1;
     if (a.D == 256 && a.G == 2) return launch_decode<256, 2>(a, st);

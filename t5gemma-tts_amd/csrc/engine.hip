@@ -1470,6 +1470,23 @@ extern "C" int t5g_sampler_setup(t5g_engine* e, int32_t B, const t5g_sampler_row
                     init[b].current_length, bound);
             return T5G_EINVAL;
         }
+    // the sampler kernels index the shared lists with each row's offsets and edit the logit
+    // of prev_token unchecked: every row's ranges must lie inside what this call uploads
+    if (n_top_k_list < 0 || n_silence < 0 || (n_top_k_list > 0 && !top_k_list) || (n_silence > 0 && !silence))
+        return T5G_EINVAL;
+    for (int b = 0; b < B; ++b) {
+        const t5g_sampler_row& r = rows[b];
+        const bool bad_silence = r.silence_off < 0 || r.n_silence < 0 ||
+                                 (r.n_silence > 0 && (int64_t)r.silence_off + r.n_silence > n_silence);
+        const bool bad_top_k = r.top_k_list_off < 0 || r.top_k_list_len < 0 ||
+                               (r.top_k_list_len > 0 && (int64_t)r.top_k_list_off + r.top_k_list_len > n_top_k_list);
+        if (bad_silence || bad_top_k || init[b].prev_token >= e->V) {
+            fprintf(stderr, "[t5gtts] row %d: silence [%d, +%d) of %d, top-k list [%d, +%d) of %d, prev_token %d of %d\n",
+                    b, r.silence_off, r.n_silence, n_silence, r.top_k_list_off, r.top_k_list_len, n_top_k_list,
+                    init[b].prev_token, e->V);
+            return T5G_EINVAL;
+        }
+    }
     hipStream_t st = (hipStream_t)stream;
     e->B = B;
     e->decode_state_invalid = false;

@@ -31,26 +31,36 @@ def _reference(q, K, V, lens, scale, causal):
     return out
 
 
-def _exact(q, K, V, lens, scale):
+def _exact(q, K, V, lens, scale, window=0):
+    """fp64 softmax attention of each row's query (at position lens[b] - 1) over its keys
+    [lo, lens[b]), lo = max(0, lens[b] - window) for a sliding window, else 0."""
     B, Hq, D = q.shape
     G = Hq // K.shape[1]
     out = torch.zeros(B, Hq, D, dtype=torch.float64)
     for b in range(B):
         L = int(lens[b])
+        lo = max(0, L - window) if window > 0 else 0
         for h in range(Hq):
-            s = (K[b, h // G, :L].double() @ q[b, h].double()) * scale
-            out[b, h] = torch.softmax(s, 0) @ V[b, h // G, :L].double()
+            s = (K[b, h // G, lo:L].double() @ q[b, h].double()) * scale
+            out[b, h] = torch.softmax(s, 0) @ V[b, h // G, lo:L].double()
     return out
 
 
-def _run(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flash=False):
+def _run(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flash=False, window=0, cap=None, prepare=None,
+         want_rc=0):
+    """One t5g_attention_decode(_flash) call on random bf16 q / K / V; returns the output
+    (fp64, [B][Hq][D]) and the host inputs. cap: cache slots per (row, kv head), default L;
+    prepare(q, K, V) edits the inputs in place before the upload; want_rc != 0: the call must
+    return that status and write nothing (returns None)."""
     from t5gemma_tts_amd import _lib
     lib = _lib.lib()
     g = torch.Generator().manual_seed(seed)
-    cap = L
+    cap = L if cap is None else cap
     q = torch.randn(B, Hq, D, generator=g).to(BF16)
     K = torch.randn(B, Hkv, cap, D, generator=g).to(BF16)
     V = torch.randn(B, Hkv, cap, D, generator=g).to(BF16)
+    if prepare is not None:
+        prepare(q, K, V)
     dev = "cuda"
     qd, Kd, Vd = q.to(dev), K.to(dev), V.to(dev)
     lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
@@ -59,10 +69,15 @@ def _run(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flash=False):
     assert nb > 0
     work = torch.zeros(nb // 4, dtype=torch.float32, device=dev)   # flash: tickets start at zero
     a = _lib.AttnDecodeArgs(B=B, n_heads=Hq, n_kv_heads=Hkv, head_dim=D, q=qd.data_ptr(), k_cache=Kd.data_ptr(),
-                            v_cache=Vd.data_ptr(), cap=cap, kv_len=lens_d.data_ptr(), causal=causal, window=0,
+                            v_cache=Vd.data_ptr(), cap=cap, kv_len=lens_d.data_ptr(), causal=causal, window=window,
                             scale=D ** -0.5, out=out.data_ptr(), work=work.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     fn = lib.t5g_attention_decode_flash if flash else lib.t5g_attention_decode
+    if want_rc != 0:
+        assert fn(C.byref(a), st) == want_rc
+        torch.cuda.synchronize()
+        assert int((out != 0).sum().item()) == 0 and int((work != 0).sum().item()) == 0   # nothing launched
+        return None
     _lib.check(fn(C.byref(a), st), "attention_decode")
     torch.cuda.synchronize()
     got = out.cpu().view(B, Hq, D).double()

@@ -95,6 +95,20 @@ def test_gemv_rejects_unsupported_shapes(layout, M, K, splits, epi, nw):
     assert L.t5g_gemv(C.byref(a), None) < 0
 
 
+@pytest.mark.parametrize("D,G", [(64, 4), (128, 1), (96, 2), (256, 4)])
+def test_attention_decode_reports_unbuilt_geometry(D, G):
+    """t5g_attention_decode / _flash answer T5G_EUNSUPPORTED on the host, before any launch, for
+    a (head_dim, group) csrc/attn.hip builds no kernel for -- in the flash form too, whose
+    thread-budget check would otherwise call it a bad argument."""
+    from t5gemma_tts_amd import _lib
+    L = _lib.lib()
+    # pointers are never dereferenced: the call is rejected before a launch
+    a = _lib.AttnDecodeArgs(B=4, n_heads=2 * G, n_kv_heads=2, head_dim=D, q=16, k_cache=16, v_cache=16, cap=200,
+                            kv_len=16, causal=1, window=0, scale=D ** -0.5, out=16, work=16)
+    assert L.t5g_attention_decode(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+    assert L.t5g_attention_decode_flash(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+
+
 def test_status_codes_map_to_python_errors():
     """The C ABI's statuses raise what the reference's code paths would (ValueError for bad
     arguments / capacity) and a FusedHandoffError for a fused decode launch whose hand-off
