@@ -658,13 +658,21 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(AttnArgs a) {
 #pragma unroll
             for (int g = 0; g < G; ++g) s[g] += q[g][2 * jj] * k0 + q[g][2 * jj + 1] * k1;
         }
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-            s[g] = xsum<LPK>(s[g]);
         const int jl = i * KPB + wave * KPW + kg;
-        if (dl == 0) {
+        if constexpr (FLASH && LPK == 32 && G == 2) {
+            // the flash launch at the 2b-2b geometry: the key's two heads reduced together
+            // (common.h xsum2_v32, as fused.hip's stage S: the same adds per head), head 0's
+            // score on the even 16-lane rows, head 1's on the odd rows
+            const float sr = xsum2_v32(s[0], s[1]);
+            if (dl % 16 == 0) sm[dl / 16][jl] = fast_score(sr, a.scale, a.softcap);
+        } else {
 #pragma unroll
-            for (int g = 0; g < G; ++g) sm[g][jl] = fast_score(s[g], a.scale, a.softcap);
+            for (int g = 0; g < G; ++g)
+                s[g] = xsum<LPK>(s[g]);
+            if (dl == 0) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) sm[g][jl] = fast_score(s[g], a.scale, a.softcap);
+            }
         }
     }
     __syncthreads();

@@ -151,6 +151,22 @@ __device__ __forceinline__ float xsum_v(float v) {
     return v;
 }
 
+// two xsum_v<32> at once: the sums of a and of b over the lanes of each 32-lane half, a's left
+// on the lanes of the even 16-lane rows, b's on the odd rows. One v_permlane16_swap exchanges
+// a's odd rows with b's even rows, so the xor-16 step of both butterflies is one add (a lane l
+// of an even row: a[l] + a[l ^ 16], of an odd row: b[l ^ 16] + b[l] -- xsum_v's pairs, and
+// fp32 addition commutes), and the in-row steps run once instead of twice: bitwise
+// xsum_v<32>(a) on the even rows and xsum_v<32>(b) on the odd rows.
+__device__ __forceinline__ float xsum2_v32(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    float v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    v += xlane<8>(v);
+    v += __builtin_amdgcn_update_dpp(0.f, v, 0x124, 0xf, 0xf, false);   // row_ror:4
+    v += xlane<2>(v);
+    v += xlane<1>(v);
+    return v;
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
     if constexpr (sizeof(T) == 4 && __is_same(T, float)) {

@@ -659,7 +659,9 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
                                              int pass = 0) {
     constexpr int G = FS_G, D = FS_D, LPK = FS_LPK, KPW = FS_KPW, KPB = FS_KPB, NIT = FS_NIT;
     const int tq = (int)threadIdx.x, wave = tq >> 6, lane = tq & 63;
-    const int grp = wave >> 2, gw = wave & 3, gt = tq & 255;
+    // (tail: the group and with it the slot's row geometry are wave-uniform, held in scalar
+    // registers across `mid`)
+    const int grp = TAIL ? __builtin_amdgcn_readfirstlane(wave >> 2) : wave >> 2, gw = wave & 3, gt = tq & 255;
     const int kg = lane / LPK, dl = lane % LPK;
     const int M = a.M, Hkv = a.Hkv;
     FbSelfGrp& L = sl.g[grp];
@@ -673,7 +675,7 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
     const int sp = has_s ? cidx / (M * Hkv) : 0, rk = has_s ? cidx - sp * (M * Hkv) : 0;
     const int m = rk / Hkv, kvh = rk - m * Hkv;
     const int dvar = FS_DBG_VAR;
-    const int len = TAIL ? len_in : a.kv_len[m];
+    const int len = TAIL ? __builtin_amdgcn_readfirstlane(len_in) : a.kv_len[m];
     int role = 0, c4 = 0, g_own = 0, col;
     if (gt < G * D / 4) {
         g_own = gt / (D / 4);
@@ -836,7 +838,10 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
         f32x2 qq[8];
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) qq[jj] = (f32x2){q[0][jj], q[1][jj]};
-        float sc[NIT][G];
+        // a key's two heads reduced together (common.h xsum2_v32: one cross-row swap and one
+        // set of in-row steps for both, the same adds as xsum_v<LPK> per head): head 0's score
+        // lands on the lanes of the even 16-lane rows, head 1's on the odd rows
+        float sc[NIT];
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
             f32x2 s2 = {0.f, 0.f};
@@ -845,15 +850,13 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
                 const float k0 = bf_lo(kr[i][jj]), k1 = bf_hi(kr[i][jj]);
                 s2 += qq[2 * jj] * k0 + qq[2 * jj + 1] * k1;
             }
-#pragma unroll
-            for (int g = 0; g < G; ++g) sc[i][g] = xsum_v<LPK>(s2[g]);   // xsum<LPK>'s adds, VALU exchanges
+            sc[i] = xsum2_v32(s2[0], s2[1]);   // xsum<LPK>'s adds, VALU exchanges
         }
         FS_TS(16);
-        if (dl == 0) {
+        if (dl % 16 == 0) {
+            const int g = dl / 16;
 #pragma unroll
-            for (int i = 0; i < NIT; ++i)
-#pragma unroll
-                for (int g = 0; g < G; ++g) L.sm[g][i * KPB + gw * KPW + kg] = fast_score(sc[i][g], a.scale, a.softcap);
+            for (int i = 0; i < NIT; ++i) L.sm[g][i * KPB + gw * KPW + kg] = fast_score(sc[i], a.scale, a.softcap);
         }
     }
     fb_lds_barrier();
