@@ -262,13 +262,13 @@ T5G_EUNSUPPORTED = -3
 # digest when the pass runs, and bench.py quotes that file's traffic only while the sources
 # still hash the same (a kernel change that keeps the kernel's name makes the file stale)
 PMC_SOURCES = {
-    "fused_block": ["fused.hip", "common.h", "t5g_kernels.h"],
-    "fused_block_s": ["fused.hip", "common.h", "t5g_kernels.h"],
+    "fused_block": ["fused.hip", "attn_chunk.h", "common.h", "t5g_kernels.h"],
+    "fused_block_s": ["fused.hip", "attn_chunk.h", "common.h", "t5g_kernels.h"],
     "fused_mlp": ["fused.hip", "common.h", "t5g_kernels.h"],
     "xlayer": ["xlayer.hip", "exact_dev.h", "exact_math.h", "common.h", "t5g_kernels.h"],
     "gate_up": ["gemv.hip", "common.h", "t5g_kernels.h"],
     # every source the fast decode step's logits and tokens depend on (fast_token_agreement)
-    "fast_path": ["fused.hip", "attn.hip", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
+    "fast_path": ["fused.hip", "attn.hip", "attn_chunk.h", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
                   "engine.hip", "engine_state.h", "common.h", "t5g_kernels.h"],
 }
 

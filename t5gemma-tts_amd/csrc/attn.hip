@@ -13,12 +13,11 @@
 // O / sum rounded once); ``eager`` mirrors eager_attention_forward (bf16 scores,
 // tanh softcap, bf16-rounded normalised probabilities).
 #include "common.h"
+#include "attn_chunk.h"
 #include "exact_math.h"
 #include "t5g_kernels.h"
 
 namespace t5g {
-
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 T5G_TS_UNIT(attn)
 
@@ -373,8 +372,8 @@ __device__ __forceinline__ void attn_flash_finish(const AttnArgs& a, float (&sm)
     const __amdgpu_buffer_rsrc_t srs = frag_rsrc(a.fstat, (uint32_t)(nrec * G * 2 * 4));
     for (int idx = tid; idx < G * LPK; idx += 256) {
         const int g = idx / LPK, d8 = idx % LPK;
-        const f32x4 lo4 = ored[0][g][d8][0] + ored[1][g][d8][0] + ored[2][g][d8][0] + ored[3][g][d8][0];
-        const f32x4 hi4 = ored[0][g][d8][1] + ored[1][g][d8][1] + ored[2][g][d8][1] + ored[3][g][d8][1];
+        f32x4 lo4, hi4;
+        fold_ored<G, LPK>(lo4, hi4, ored, g, d8);
         const int off = (int)((((rec + sp) * G + g) * D + 8 * d8) * 4);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo4), prs, off, 0, 16);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi4), prs, off + 16, 0, 16);
@@ -451,8 +450,7 @@ __device__ __forceinline__ void attn_flash_finish(const AttnArgs& a, float (&sm)
             acc += w * pv[k];
         }
     }
-    const float inv = 1.0f / lsum[og];
-    const u32x2_t ow = {pack2(acc[0] * inv, acc[1] * inv), pack2(acc[2] * inv, acc[3] * inv)};
+    const u32x2_t ow = flash_combine_pack(acc, lsum[og]);
     *(u32x2_t*)(a.O + (long)qi * a.ldo + (kvh * G + og) * D + 4 * o4) = ow;
     T5G_TS_BY(5, 64 * G);
 }
@@ -572,13 +570,8 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(AttnArgs a) {
 #pragma unroll
         for (int s = 1; s < QSMAX; ++s)
             if (s < a.q_nsplit) acc += u[s];
-        if (role == 0) {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) qs[g_own][4 * c4 + jj] = rbf(acc[jj]);
-        } else if (role > 0) {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) kvnew[role - 1][4 * c4 + jj] = rbf(acc[jj]);
-        }
+        if (role == 0) stage_round4(&qs[g_own][4 * c4], acc);
+        else if (role > 0) stage_round4(&kvnew[role - 1][4 * c4], acc);
         if (!a.rope_tab) {
             const float ps = a.pos[row];
 #pragma unroll
@@ -710,8 +703,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(AttnArgs a) {
     if (wave < G) {
         const int g = wave;
         const float s = lane < n ? sm[g][lane] : -INFINITY;
-        const float mx = wave_max(s);
-        const float p = lane < n ? sdpa_p(__fsub_rn(s, mx), lane, span) : 0.f;
+        const float p = one_block_p(s, lane < n, lane, span);
         pl[g][lane] = p;
         if (lane < 16) pl[g][DCH + lane] = 0.f;
         sm[g][lane] = rbf(p);
@@ -755,15 +747,9 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(AttnArgs a) {
     T5G_TS(4);
     for (int idx = threadIdx.x; idx < G * LPK; idx += 256) {
         const int g = idx / LPK, d8 = idx % LPK;
-        const f32x4 lo4 = ored[0][g][d8][0] + ored[1][g][d8][0] + ored[2][g][d8][0] + ored[3][g][d8][0];
-        const f32x4 hi4 = ored[0][g][d8][1] + ored[1][g][d8][1] + ored[2][g][d8][1] + ored[3][g][d8][1];
-        const float inv = __fdiv_rn(1.0f, stat_l[g]);
-        u32x4 w;
-        w[0] = pack2(__fmul_rn(lo4[0], inv), __fmul_rn(lo4[1], inv));
-        w[1] = pack2(__fmul_rn(lo4[2], inv), __fmul_rn(lo4[3], inv));
-        w[2] = pack2(__fmul_rn(hi4[0], inv), __fmul_rn(hi4[1], inv));
-        w[3] = pack2(__fmul_rn(hi4[2], inv), __fmul_rn(hi4[3], inv));
-        *(u32x4*)(a.O + (long)qi * a.ldo + (kvh * G + g) * D + 8 * d8) = w;
+        f32x4 lo4, hi4;
+        fold_ored<G, LPK>(lo4, hi4, ored, g, d8);
+        *(u32x4*)(a.O + (long)qi * a.ldo + (kvh * G + g) * D + 8 * d8) = normalise_pack(lo4, hi4, stat_l[g]);
     }
     T5G_TS(5);
 }

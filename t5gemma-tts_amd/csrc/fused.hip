@@ -29,6 +29,7 @@
 // per-wave k-step chains, the same fixed-order wave reductions, the same norm reductions),
 // so the fused launch is bitwise equal to the three launches (tests/test_gpu_fused.py).
 #include "common.h"
+#include "attn_chunk.h"
 #include "t5g_kernels.h"
 
 namespace t5g {
@@ -116,7 +117,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, uin
                                              (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 constexpr int AUX_NT = 2, AUX_SC1 = 16;
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void unpack8f(u32x4 w, float (&v)[8]) {
 #pragma unroll
@@ -739,13 +739,8 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
         if constexpr (!TAIL) {
             f32x4 acc = u0;
             acc += u1;
-            if (role == 0) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) L.qs[g_own][4 * c4 + jj] = rbf(acc[jj]);
-            } else if (has_t) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) L.kvnew[role - 1][4 * c4 + jj] = rbf(acc[jj]);
-            }
+            if (role == 0) stage_round4(&L.qs[g_own][4 * c4], acc);
+            else if (has_t) stage_round4(&L.kvnew[role - 1][4 * c4], acc);
         }
         // the RoPE row consumed here too (an empty asm use): past the branch join the compiler
         // would otherwise wait for nearly every K / V request before the q rotation
@@ -773,13 +768,8 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
         if (gv) {
             f32x4 acc = u0;
             acc += u1;
-            if (role == 0) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) L.qs[g_own][4 * c4 + jj] = rbf(acc[jj]);
-            } else if (has_t) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) L.kvnew[role - 1][4 * c4 + jj] = rbf(acc[jj]);
-            }
+            if (role == 0) stage_round4(&L.qs[g_own][4 * c4], acc);
+            else if (has_t) stage_round4(&L.kvnew[role - 1][4 * c4], acc);
         }
     }
     fb_lds_barrier();
@@ -867,7 +857,7 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
         const float s = lane < n ? L.sm[g][lane] : -INFINITY;
         const float mx = wave_max(s);
         if (single) {
-            const float p = lane < n ? sdpa_p(__fsub_rn(s, mx), lane, span) : 0.f;
+            const float p = lane < n ? sdpa_p(__fsub_rn(s, mx), lane, span) : 0.f;   // (attn_chunk.h one_block_p; mx is the flash branch's too)
             L.pl[g][lane] = p;
             if (lane < 16) L.pl[g][FS_CH + lane] = 0.f;
             L.sm[g][lane] = rbf(p);
@@ -917,15 +907,10 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
     FS_TS(4);
     if (gv && gt < G * LPK) {
         const int g = gt / LPK, d8 = gt % LPK;
-        const f32x4 lo4 = L.ored[0][g][d8][0] + L.ored[1][g][d8][0] + L.ored[2][g][d8][0] + L.ored[3][g][d8][0];
-        const f32x4 hi4 = L.ored[0][g][d8][1] + L.ored[1][g][d8][1] + L.ored[2][g][d8][1] + L.ored[3][g][d8][1];
+        f32x4 lo4, hi4;
+        fold_ored<G, LPK>(lo4, hi4, L.ored, g, d8);
         if (single) {   // the row's output
-            const float inv = __fdiv_rn(1.0f, L.stat_l[g]);
-            u32x4 w;
-            w[0] = pack2(__fmul_rn(lo4[0], inv), __fmul_rn(lo4[1], inv));
-            w[1] = pack2(__fmul_rn(lo4[2], inv), __fmul_rn(lo4[3], inv));
-            w[2] = pack2(__fmul_rn(hi4[0], inv), __fmul_rn(hi4[1], inv));
-            w[3] = pack2(__fmul_rn(hi4[2], inv), __fmul_rn(hi4[3], inv));
+            const u32x4 w = normalise_pack(lo4, hi4, L.stat_l[g]);
             __builtin_amdgcn_raw_buffer_store_b128(w, ors, (m * a.q_dim + (kvh * G + g) * D + 8 * d8) * 2, 0, AUX_SC1);
         } else {        // the chunk's partial
             const int off = (int)(((((long)m * Hkv + kvh) * a.s_nsplit + sp) * G + g) * D + 8 * d8) * 4;
@@ -1008,8 +993,7 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
                     acc += w * pv[k];
                 }
             }
-            const float inv = 1.0f / L.lsum[og];
-            const u32x2_t ow = {pack2(acc[0] * inv, acc[1] * inv), pack2(acc[2] * inv, acc[3] * inv)};
+            const u32x2_t ow = flash_combine_pack(acc, L.lsum[og]);
             __builtin_amdgcn_raw_buffer_store_b64(ow, ors, (m * a.q_dim + (kvh * G + og) * D + 4 * o4) * 2, 0,
                                                   AUX_SC1);
         }
@@ -1357,8 +1341,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
         if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {   // a head's first wave
             const float sc = lane < n ? al.sm[lane] : -INFINITY;
-            const float mx = wave_max(sc);
-            const float p = lane < n ? sdpa_p(__fsub_rn(sc, mx), lane, span) : 0.f;
+            const float p = one_block_p(sc, lane < n, lane, span);
             al.pl[lane] = p;
             if (lane < 16) al.pl[64 + lane] = 0.f;
             al.sm[lane] = rbf(p);
@@ -1391,14 +1374,10 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
         if ((MT == 1 ? tq < LPK : (tq & ~256) < LPK) && n > 0) {
             const int d8 = at;
+            // (attn_chunk.h fold_ored's order; called here, the two-tile kernels' schedule moves)
             const f32x4 lo4 = al.ored[0][d8][0] + al.ored[1][d8][0] + al.ored[2][d8][0] + al.ored[3][d8][0];
             const f32x4 hi4 = al.ored[0][d8][1] + al.ored[1][d8][1] + al.ored[2][d8][1] + al.ored[3][d8][1];
-            const float inv = __fdiv_rn(1.0f, al.stat_l);
-            u32x4 w;
-            w[0] = pack2(__fmul_rn(lo4[0], inv), __fmul_rn(lo4[1], inv));
-            w[1] = pack2(__fmul_rn(lo4[2], inv), __fmul_rn(lo4[3], inv));
-            w[2] = pack2(__fmul_rn(hi4[0], inv), __fmul_rn(hi4[1], inv));
-            w[3] = pack2(__fmul_rn(hi4[2], inv), __fmul_rn(hi4[3], inv));
+            const u32x4 w = normalise_pack(lo4, hi4, al.stat_l);
             const __amdgpu_buffer_rsrc_t orr = raw_rsrc(a.att, (uint32_t)(M * a.q_dim * 2));
             __builtin_amdgcn_raw_buffer_store_b128(w, orr, (am * a.q_dim + ah * D + 8 * d8) * 2, 0, AUX_SC1);
         }
