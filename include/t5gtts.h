@@ -126,6 +126,26 @@ int64_t t5g_packed_bytes(int32_t N, int32_t K);
 /* Pack src_dev [N][K] (row stride ld elements) into dst_dev (t5g_packed_bytes(N,K) bytes). */
 int t5g_pack_weight(const void* src_dev, int32_t N, int32_t K, int64_t ld, void* dst_dev, void* stream);
 
+/* --- FP8 weights for the fast decode step (opt-in; csrc/fp8.hip) ------
+ * Format "P8" of an [N][K] Linear (K % 32 == 0): OCP e4m3fn codes in P16's fragment and lane
+ * order (512 bytes per 16 rows x 32 k, 16 * ceil(N / 16) rows: not padded to 64) and one fp32
+ * scale 2^e per output row (16 * ceil(N / 16) entries; padded rows: codes 0, scale 1). Per row:
+ * e = the smallest integer >= -100 with max|W[n, :]| * 2^-e <= 448 (0 for an all-zero row),
+ * code = RNE_e4m3fn(W * 2^-e); the NaN codes are never produced and W_q = 2^e * code is
+ * exactly bf16. No reference-side equivalent (the reference keeps bf16 weights). */
+/* Bytes of the P8 codes of an [N][K] matrix; host only. No reference-side equivalent. */
+int64_t t5g_fp8_packed_bytes(int32_t N, int32_t K);
+/* Quantise src_dev bf16 [N][K] (row stride ld elements, ld % 8 == 0) into p8_dev
+ * (t5g_fp8_packed_bytes(N, K) bytes), scale_dev (16 * ceil(N / 16) floats) and, unless NULL,
+ * wq_dev: the dequantised bf16 [N][K] image W_q (pack it with t5g_pack_weight for the phases
+ * that keep the bf16 kernels). A non-finite weight is T5G_EINVAL. Synchronous. No
+ * reference-side equivalent. */
+int t5g_quantize_weight_fp8(const void* src_dev, int32_t N, int32_t K, int64_t ld, void* p8_dev, float* scale_dev,
+                            void* wq_dev /* bf16 [N][K], may be NULL */, void* stream);
+/* Test hook: P8 -> row-major bf16 [N][K] through the kernels' own convert
+ * (v_cvt_scalef32_pk_bf16_fp8, csrc/fp8.h p8_to_bf16). No reference-side equivalent. */
+int t5g_fp8_unpack(const void* p8_dev, const float* scale_dev, int32_t N, int32_t K, void* out_bf16_dev, void* stream);
+
 /* --- engine lifetime --------------------------------------------------------- */
 /* Replaces T5GemmaVoiceForConditionalGeneration.__init__ (:343-479) for the
  * inference path: binds caller-owned device weights, allocates the KV arena and
@@ -133,6 +153,36 @@ int t5g_pack_weight(const void* src_dev, int32_t N, int32_t K, int64_t ld, void*
 int t5g_engine_create(const t5g_config* cfg, const t5g_weights* w, t5g_engine** out);
 int t5g_engine_destroy(t5g_engine* e);
 int64_t t5g_engine_workspace_bytes(const t5g_engine* e);
+
+/* FP8 mode of the fast decode step (opt-in): the P8 images + row scales of what a decode step
+ * streams -- every decoder layer's six Linears (gate_up in the interleaved row order of
+ * t5g_layer_weights.gate_up) and head2. The P16 weights the engine was created with must be
+ * the images of the same W_q (t5g_quantize_weight_fp8's wq_dev, packed): encoder, prefill,
+ * head1 and any fallback GEMM keep reading them, so one engine computes with one set of
+ * weights throughout, and a decode step is bitwise the bf16 fast path on W_q.
+ * Call after t5g_engine_create and before the first decode; the pointers are caller-owned and
+ * the host arrays are copied. NULL turns FP8 off. Needs the widths the register-X GEMV sites
+ * are built for (hidden 2304, intermediate 9216, q_dim 2048; else T5G_EUNSUPPORTED); refused
+ * in parity mode, and t5g_engine_set_exact(e, 1, ...) on an FP8 engine is T5G_EUNSUPPORTED.
+ * In FP8 mode every decode batch (1-32 rows) runs the per-op launches with the P8 GEMVs and
+ * the head on the P8 GEMV: the persistent layer launches are built for bf16 weights only, so
+ * t5g_engine_set_fused does not change an FP8 engine's launches and t5g_time_decode_layer /
+ * t5g_time_decode_mlp are T5G_EUNSUPPORTED. More than 32 rows: the bf16 kernels on W_q.
+ * No reference-side equivalent. */
+typedef struct {
+    const void* p8;        /* P8 codes, t5g_fp8_packed_bytes(N, K) bytes */
+    const float* scale;    /* fp32 [16 * ceil(N / 16)] */
+} t5g_fp8_linear;
+typedef struct {
+    t5g_fp8_linear qkv, o, cross_q, cross_o, gate_up, down;
+} t5g_fp8_layer;
+typedef struct {
+    const t5g_fp8_layer* dec_layers;   /* host array [n_dec_layers] */
+    t5g_fp8_linear head2;
+} t5g_fp8_weights;
+int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* w);
+/* *fmt = 0: bf16 weights, 1: FP8 mode. No reference-side equivalent. */
+int t5g_engine_weight_format(t5g_engine* e, int32_t* fmt);
 
 /* --- generate() phases --------------------------------------------------------
  * Token batches are PACKED: ntok tokens of B rows, with per-token row index
@@ -263,6 +313,12 @@ typedef struct {
                                  P16 either way; -1 for any other shape */
 } t5g_gemv_args;
 int t5g_gemv(const t5g_gemv_args* args, void* stream);
+/* The register-resident-X GEMV on FP8 weights: args->W is a P8 image, scale_dev its row scales
+ * (t5g_quantize_weight_fp8). Layout 1 only, and the shapes t5g_gemv accepts there; anything
+ * else returns what t5g_gemv returns for an unbuilt shape, decided on the host. The fragments
+ * are converted to bf16 with the row scale as the convert's scale operand, once per unit, so
+ * the result is bitwise t5g_gemv on the P16 image of W_q. No reference-side equivalent. */
+int t5g_gemv_fp8(const t5g_gemv_args* args, const float* scale_dev, void* stream);
 /* The decode step's residual + RMSNorm pair on caller buffers (norm.hip, [tf] T5GemmaRMSNorm
  * :61-78 wired as PMDecoderLayer :285-323): resid_out = bf16(resid + RMSNorm(1+post_w)(delta)),
  * normed_out = RMSNorm(1+pre_w)(resid_out); bf16 [M][d] rows. For parity tests. */

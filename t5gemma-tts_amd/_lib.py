@@ -63,6 +63,19 @@ class Weights(C.Structure):
                 ("enc_layers", C.POINTER(LayerWeights)), ("dec_layers", C.POINTER(LayerWeights))]
 
 
+class Fp8Linear(C.Structure):
+    _fields_ = [("p8", C.c_void_p), ("scale", C.c_void_p)]
+
+
+class Fp8Layer(C.Structure):
+    _fields_ = [("qkv", Fp8Linear), ("o", Fp8Linear), ("cross_q", Fp8Linear), ("cross_o", Fp8Linear),
+                ("gate_up", Fp8Linear), ("down", Fp8Linear)]
+
+
+class Fp8Weights(C.Structure):
+    _fields_ = [("dec_layers", C.POINTER(Fp8Layer)), ("head2", Fp8Linear)]
+
+
 class SamplerRow(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("top_k_list_len", C.c_int32), ("top_k_list_off", C.c_int32),
                 ("top_p", C.c_float), ("min_p", C.c_float), ("temperature", C.c_float),
@@ -99,6 +112,12 @@ _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
     "t5g_packed_bytes": (_L, [_I, _I]),
     "t5g_pack_weight": (C.c_int, [_P, _I, _I, _L, _P, _P]),
+    "t5g_fp8_packed_bytes": (_L, [_I, _I]),
+    "t5g_quantize_weight_fp8": (C.c_int, [_P, _I, _I, _L, _P, _P, _P, _P]),
+    "t5g_fp8_unpack": (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    "t5g_gemv_fp8": (C.c_int, [C.POINTER(GemvArgs), _P, _P]),
+    "t5g_engine_set_fp8_weights": (C.c_int, [_P, C.POINTER(Fp8Weights)]),
+    "t5g_engine_weight_format": (C.c_int, [_P, C.POINTER(_I)]),
     "t5g_engine_create": (C.c_int, [C.POINTER(Config), C.POINTER(Weights), C.POINTER(_P)]),
     "t5g_engine_destroy": (C.c_int, [_P]),
     "t5g_engine_workspace_bytes": (_L, [_P]),

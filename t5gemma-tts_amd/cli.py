@@ -90,12 +90,14 @@ def load_codec(codec_dir: Optional[str] = None, codec: str = "44k", device="cuda
 
 
 def load_model(model_dir: Optional[str] = None, synthetic: Optional[str] = None, device="cuda:0",
-               max_text: int = 512, max_audio: Optional[int] = None, seed: int = 7):
+               max_text: int = 512, max_audio: Optional[int] = None, seed: int = 7, weight_format: str = "bf16"):
     """The voice model, sized for the reference CLI's longest request by default (max_audio =
     engine.MAX_AUDIO keys: a 100 s prompt + the 120 s duration cap; 1.3 GB of KV cache at
-    batch 1) -- a shorter request runs on its own key bound, not the capacity."""
+    batch 1) -- a shorter request runs on its own key bound, not the capacity.
+    ``weight_format="fp8"``: the decode step streams FP8 e4m3 weights (fast path only)."""
     from .engine import MAX_AUDIO, T5GemmaVoiceForConditionalGeneration
-    kw = dict(device=device, max_batch=1, max_text=max_text, max_audio=MAX_AUDIO if max_audio is None else max_audio)
+    kw = dict(device=device, max_batch=1, max_text=max_text, max_audio=MAX_AUDIO if max_audio is None else max_audio,
+              weight_format=weight_format)
     if synthetic:
         from .config import named_config
         from .weights import synthetic_weights
@@ -112,20 +114,30 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
                   repeat_prompt=0, stop_repetition=3, sample_batch_size=1, seed=1, output_dir="./generated_tts",
                   cut_off_sec=100, dump_tokens=False, lang=None, codec_dir=None, tokenizer_dir=None, synthetic=None,
                   codec="44k", device="cuda:0", whisper_model="large-v3-turbo", model=None, audio_tokenizer=None,
-                  text_tokenizer=None, asr_model=None, parity=True):
+                  text_tokenizer=None, asr_model=None, parity=True, weight_format="bf16"):
     """inference_commandline_hf.py:72-242. ``model`` / ``audio_tokenizer`` /
     ``text_tokenizer`` / ``asr_model`` may be passed pre-built (then nothing is loaded).
     ``parity`` (default True, ``--parity False`` on the command line): reproduce the
     reference's tokens bit for bit (exact-order kernels, reference RNG stream, one host sync
     per step); False runs the fast graph-replayed path with on-device noise.
+    ``weight_format`` ("bf16" default, ``--weight_format fp8``): "fp8" quantises the decode
+    step's weights to FP8 e4m3 with power-of-two row scales when the model is loaded (DESIGN.md
+    §5 "FP8 mode"); it is fast path only, so the run is made with ``parity=False``. An unknown
+    value raises ValueError before anything is loaded.
     Returns the path of the written wav."""
+    from .weights import WEIGHT_FORMATS
+    if weight_format not in WEIGHT_FORMATS:
+        raise ValueError(f"weight_format {weight_format!r}: one of {WEIGHT_FORMATS}")
+    if weight_format == "fp8" and parity:
+        print("[Info] weight_format fp8 is fast path only: running with parity=False")
+        parity = False
     from .audio import audio_info, write_wav
     from .pipeline import inference_one_sample, parse_silence_tokens
     from .text import estimate_duration, load_text_tokenizer, normalize_text_with_lang
 
     seed_everything(seed)
     if model is None:
-        model = load_model(model_dir, synthetic, device)
+        model = load_model(model_dir, synthetic, device, weight_format=weight_format)
     cfg = model.config
     if text_tokenizer is None:
         if synthetic and _none(tokenizer_dir):
@@ -218,7 +230,7 @@ def _arg(v: str):
 
 _SIGNATURE_OF = run_inference   # the flags (main() calls whatever run_inference is bound to)
 _STR_ARGS = {"reference_speech", "target_text", "model_dir", "reference_text", "output_dir", "lang", "codec_dir",
-             "tokenizer_dir", "synthetic", "codec", "device", "whisper_model"}
+             "tokenizer_dir", "synthetic", "codec", "device", "whisper_model", "weight_format"}
 
 
 def main(argv=None) -> None:

@@ -12,6 +12,7 @@
 // The engine's state is engine_state.h; the timing hooks (t5g_time_*) and the stand-alone op
 // wrappers for tests and probes are engine_hooks.hip.
 #include "engine_state.h"
+#include "fp8.h"
 
 constexpr int GRAPH_STEPS = 8;   // decode iterations per multi-step graph
 
@@ -788,6 +789,7 @@ extern "C" int t5g_engine_set_exact(t5g_engine* e, int32_t enable, const uint16_
         e->exact = false;
         return T5G_OK;
     }
+    if (e->fp8) return T5G_EUNSUPPORTED;   // FP8 mode is fast path only (the reference has bf16 weights)
     if (threads != REF_KSPLIT_THREADS) return T5G_EUNSUPPORTED;   // the only measured K-split table
     // eager attention (softcap): restated for the measured call shape (8 query heads of 256,
     // eager.hip) once the reference host's tanh table is set (t5g_engine_set_tanh_lut)
@@ -805,6 +807,37 @@ extern "C" int t5g_engine_set_exact(t5g_engine* e, int32_t enable, const uint16_
     e->exact_threads = threads;
     if (!e->exact) drop_graphs(e);
     e->exact = true;
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* w) {
+    if (!e) return T5G_EINVAL;
+    if (e->exact) return T5G_EUNSUPPORTED;   // parity mode reproduces the reference's bf16 weights
+    if (w) {
+        const t5g_config& c = e->c;
+        // the widths of the register-X GEMV sites (decode_plan): only those run on P8
+        if (c.hidden != 2304 || c.intermediate != 9216 || e->q_dim != 2048) return T5G_EUNSUPPORTED;
+        if (!w->dec_layers || !w->head2.p8 || !w->head2.scale) return T5G_EINVAL;
+        for (int l = 0; l < c.n_dec_layers; ++l) {
+            const t5g_fp8_layer& L = w->dec_layers[l];
+            for (const t5g_fp8_linear* x : {&L.qkv, &L.o, &L.cross_q, &L.cross_o, &L.gate_up, &L.down})
+                if (!x->p8 || !x->scale) return T5G_EINVAL;
+        }
+    }
+    drop_graphs(e);   // captured steps hold the other format's launches
+    e->fp8 = w != nullptr;
+    e->dec8.clear();
+    e->head2_8 = {nullptr, nullptr};
+    if (w) {
+        e->dec8.assign(w->dec_layers, w->dec_layers + e->c.n_dec_layers);
+        e->head2_8 = w->head2;
+    }
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_weight_format(t5g_engine* e, int32_t* fmt) {
+    if (!e || !fmt) return T5G_EINVAL;
+    *fmt = e->fp8 ? 1 : 0;
     return T5G_OK;
 }
 
@@ -1134,6 +1167,8 @@ DecodePlan decode_plan(t5g_engine* e, int M, int block_rows, bool switches) {
     p.mlp_half = e->fused_mlp && rows32 && wd && wf && c.n_dec_layers >= 2;
     p.block = M <= block_rows && (!switches || (p.mlp_half && wq));
     // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
+    // FP8 mode: per-op launches at every batch size (the persistent launches stream bf16 only)
+    if (e->fp8) p.mlp_half = p.block = false;
     p.tail = p.block && e->attn_in_block == 2 && (!switches || e->attn_flash);
     for (int l = 0; l < c.n_dec_layers && p.tail; ++l) {
         FusedMlpArgs fa = fused_block_args(e, M, l);
@@ -1248,17 +1283,21 @@ static int prefill_pass(t5g_engine* e, int M, const int* ids, const int* tok_row
 // A decode Linear at one of the plan's sites: on the GEMV when the site has one, on the tiled
 // GEMM (gemm_splits k-slices) otherwise or when the GEMV reports -1 (its per-block LDS does
 // not fit this device's CU count, e.g. a CPX partition). *on_gemv: which of the two ran.
+// w8 (FP8 mode, register-X sites only): the P8 image + row scales of the same Linear; the GEMV
+// streams those, the GEMM fallback the P16 image of W_q.
 static int rx_or_gemm(const GemvSite& gv, int gemm_splits, const bf16_t* X, int M, const void* W, int N, int K,
-                      void* Y, int ldy, int epi, hipStream_t st, bool* on_gemv = nullptr) {
+                      void* Y, int ldy, int epi, hipStream_t st, bool* on_gemv = nullptr,
+                      const t5g_fp8_linear* w8 = nullptr) {
     if (on_gemv) *on_gemv = false;
     if (gv.nw) {
-        DecGemmArgs g = dec_args(M, W, N, K, Y, ldy, gv.nw);
+        const bool p8 = w8 && w8->p8 && gv.rx;
+        DecGemmArgs g = dec_args(M, p8 ? w8->p8 : W, N, K, Y, ldy, gv.nw);
         g.X = X;
         g.ldx = K;
         g.splits = gv.splits;
         g.un = gv.un;
         g.layout_rx = gv.rx;
-        const int rc = gemv_dec(g, epi, st);
+        const int rc = p8 ? gemv_rx_p8(g, w8->scale, epi, st) : gemv_dec(g, epi, st);
         if (rc != -1) {
             if (on_gemv) *on_gemv = rc == 0;
             return rc;
@@ -1300,8 +1339,8 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
                                 c.dec_sliding[l] ? c.sliding_window : 0, 0, true, pos, tab, s_qkv, e->qkv_dim, st);
     };
     // attention output projection into the norm's slabs
-    auto out_proj = [&](const void* W) -> int {
-        return rx_or_gemm(p.proj, s_o, e->datt, M, W, d, e->q_dim, e->part, d, EPI_F32, st);
+    auto out_proj = [&](const void* W, const t5g_fp8_linear* w8) -> int {
+        return rx_or_gemm(p.proj, s_o, e->datt, M, W, d, e->q_dim, e->part, d, EPI_F32, st, nullptr, w8);
     };
     NormArgs n0 = embed_norm_args(e, M, e->next_token, e->dh, e->dxn);
     n0.rope_pos = pos;   // and the step's RoPE table, in the same launch
@@ -1313,9 +1352,11 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
     bool qkv_done = false;   // the previous layer's fused block projected this layer's q|k|v
     for (int l = 0; l < c.n_dec_layers; ++l) {
         const t5g_layer_weights& L = e->dec[l];
+        const t5g_fp8_layer* L8 = e->fp8 ? &e->dec8[l] : nullptr;   // FP8 mode: the layer's P8 images
         const bool last = l == c.n_dec_layers - 1;
         if (!qkv_done)
-            RC(rx_or_gemm(p.qkv, s_qkv, e->dxn, M, L.qkv, e->qkv_dim, d, e->part, e->qkv_dim, EPI_F32, st));
+            RC(rx_or_gemm(p.qkv, s_qkv, e->dxn, M, L.qkv, e->qkv_dim, d, e->part, e->qkv_dim, EPI_F32, st, nullptr,
+                          L8 ? &L8->qkv : nullptr));
         qkv_done = false;
         FusedMlpArgs fa;
         if (p.tail) {
@@ -1324,7 +1365,7 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
             // o-projection at its end (bitwise equal to the launches below)
             if (l == 0) {
                 RC(self_attention(l));
-                RC(out_proj(L.o));
+                RC(out_proj(L.o, nullptr));
             }
             fa = fused_block_args(e, M, l);
             if (!fused_block_tail(e, l, fa)) return T5G_EUNSUPPORTED;   // the plan checked every layer
@@ -1351,23 +1392,26 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
             continue;
         }
         RC(self_attention(l));
-        RC(out_proj(L.o));
+        RC(out_proj(L.o, L8 ? &L8->o : nullptr));
         RC(resid(s_o, L.norms[1], L.norms[2]));
         // --- PM cross attention (q rotated by the decoder progress, :149-165); the GEMM
         // fallback of cross-q writes s_o slabs, the GEMV its own two
         bool q_gemv = false;
-        RC(rx_or_gemm(p.cross_q, s_o, e->dxn, M, L.cross_q, e->q_dim, d, e->part, e->q_dim, EPI_F32, st, &q_gemv));
+        RC(rx_or_gemm(p.cross_q, s_o, e->dxn, M, L.cross_q, e->q_dim, d, e->part, e->q_dim, EPI_F32, st, &q_gemv,
+                      L8 ? &L8->cross_q : nullptr));
         RC(decode_attention(e, M, e->ck[l], e->cv[l], c.max_text, e->enc_len, 0, 0, 0, false, pos, tab,
                             q_gemv ? p.cross_q.splits : s_o, e->q_dim, st));
-        RC(out_proj(L.cross_o));
+        RC(out_proj(L.cross_o, L8 ? &L8->cross_o : nullptr));
         // --- norm + GeGLU MLP as one persistent launch (fused.hip; bitwise equal to the three
         // launches below); -1: a shape / device the launch is not built for
         const int rc = launch == DL_MLP_HALF ? fused_mlp(fa, st) : -1;
         if (rc != 0) {
             if (rc != -1) RC(rc);
             RC(resid(s_o, L.norms[3], L.norms[4]));
-            RC(rx_or_gemm(p.gate_up, 1, e->dxn, M, L.gate_up, 2 * f, d, e->dact, f, EPI_GEGLU, st));
-            RC(rx_or_gemm(p.down, s_down, e->dact, M, L.down, d, f, e->part, d, EPI_F32, st));
+            RC(rx_or_gemm(p.gate_up, 1, e->dxn, M, L.gate_up, 2 * f, d, e->dact, f, EPI_GEGLU, st, nullptr,
+                          L8 ? &L8->gate_up : nullptr));
+            RC(rx_or_gemm(p.down, s_down, e->dact, M, L.down, d, f, e->part, d, EPI_F32, st, nullptr,
+                          L8 ? &L8->down : nullptr));
         }
         RC(resid(s_down, L.norms[5], last ? e->w.dec_final_norm : e->dec[l + 1].norms[0]));
     }
@@ -1396,13 +1440,14 @@ static int head(t5g_engine* e, const bf16_t* xn_rows, int B, hipStream_t st) {
         // 56.3 us at 8 rows, 58.6 vs 103.1 at 32). 4 waves at every batch size: above 16 rows
         // only 4 waves' partial sums (17 units x 2 tiles x 4 waves x 1 KiB) fit LDS, and one
         // wave count keeps a row's logits independent of the batch
-        DecGemmArgs g = dec_args(B, e->w.head2, e->V, d, e->logits, e->logits_ld, 4);
+        // FP8 mode: the same launch on head2's P8 image
+        DecGemmArgs g = dec_args(B, e->fp8 ? e->head2_8.p8 : e->w.head2, e->V, d, e->logits, e->logits_ld, 4);
         g.X = e->dhh;
         g.ldx = d;
         g.un = 8;
         g.layout_rx = 1;
         g.bias = (const bf16_t*)e->w.head2_bias;
-        const int rc = gemv_dec(g, EPI_BIAS_BF16, st);
+        const int rc = e->fp8 ? gemv_rx_p8(g, e->head2_8.scale, EPI_BIAS_BF16, st) : gemv_dec(g, EPI_BIAS_BF16, st);
         if (rc == -1)
             RC(gemm(e->dhh, d, B, e->w.head2, e->V, d, 1, e->w.head2_bias, e->logits, e->logits_ld, EPI_BIAS_BF16, st));
         else RC(rc);

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "engine_state.h"
+#include "fp8.h"
 
 // Mean microseconds of n calls of body(i) -> T5G code, between two events recorded on st
 // around the calls (warm-up launches belong before this). The events are destroyed on every
@@ -167,6 +168,7 @@ extern "C" int t5g_time_xlayer(t5g_engine* e, int32_t B, int32_t iters, void* st
 // launch streams its weights from HBM (2.2 GB of gate/up + down > the 256 MiB Infinity Cache)
 extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
     if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
+    if (e->fp8) return T5G_EUNSUPPORTED;   // the persistent launches stream bf16 weights only
     e->decode_state_invalid = true;
     hipStream_t st = (hipStream_t)stream;
     const int L = e->c.n_dec_layers;
@@ -197,6 +199,7 @@ extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void
 extern "C" int t5g_time_decode_layer(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us,
                                      float* keys) {
     if (!e || iters <= 0 || !avg_us || !keys || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
+    if (e->fp8) return T5G_EUNSUPPORTED;   // the persistent launches stream bf16 weights only
     e->decode_state_invalid = true;
     hipStream_t st = (hipStream_t)stream;
     const t5g_config& c = e->c;
@@ -355,6 +358,15 @@ extern "C" int t5g_gemv(const t5g_gemv_args* g, void* stream) {
     int rc = gemv_from_abi(g, g ? g->W : nullptr, &a);
     if (rc) return rc;
     RC(gemv_dec(a, g->epi, (hipStream_t)stream));
+    return T5G_OK;
+}
+
+extern "C" int t5g_gemv_fp8(const t5g_gemv_args* g, const float* scale, void* stream) {
+    DecGemmArgs a;
+    int rc = gemv_from_abi(g, g ? g->W : nullptr, &a);
+    if (rc) return rc;
+    if (!scale) return T5G_EINVAL;
+    RC(gemv_rx_p8(a, scale, g->epi, (hipStream_t)stream));   // -1 (layout 0, an unbuilt shape): as t5g_gemv
     return T5G_OK;
 }
 

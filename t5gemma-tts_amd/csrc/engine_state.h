@@ -139,6 +139,13 @@ struct t5g_engine {
     // t5g_sampler_setup (after a fresh prefill) starts a new call
     bool decode_state_invalid = false;
     int64_t xl_launches = 0;   // xlayer.hip launches issued (captured ones counted once, at capture)
+    // FP8 mode (t5g_engine_set_fp8_weights): the P8 images + row scales of the decode step's
+    // Linears; the P16 pointers above are then the images of the same W_q. The fast decode
+    // step runs its register-X GEMV sites and the head on them (per-op launches at every
+    // batch size: the persistent launches stream bf16 weights only)
+    bool fp8 = false;
+    std::vector<t5g_fp8_layer> dec8;
+    t5g_fp8_linear head2_8 = {nullptr, nullptr};
 };
 
 // ---- the fast decode step's launch plan (engine.hip) ------------------------------------

@@ -8,7 +8,9 @@
 // Optional split-K over blockIdx.y writes fp32 slabs (EPI_F32) for the consumer to sum.
 // The decode step runs its gate/up projection here (engine.hip decoder_pass).
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
+#include "fp8.h"
 #include "t5g_kernels.h"
 
 namespace t5g {
@@ -206,8 +208,16 @@ __global__ __launch_bounds__(NW * 64) void gemv_dec_kernel(DecGemmArgs a) {
 // UMAX > 0: every unit's weight batch is requested before the first multiply (up to UMAX
 // units per block held in registers) instead of one unit ahead -- the block's whole weight
 // stream is in flight from the start.
-template <int NW, int MT, int EPI, int SPU, int UMAX = 0>
-__global__ __launch_bounds__(NW * 64) void gemv_rx_kernel(DecGemmArgs a) {
+// P8: the weights are an FP8 image (fp8.h) -- 8-byte fragment loads, the lane's row scale loaded
+// once per unit, and each fragment converted to bf16 (scaled: exactly W_q) once per unit in
+// front of its MFMAs. Everything else is the bf16 instantiation, so the results are bitwise
+// those of the bf16 kernel on the P16 image of W_q.
+struct DecGemmArgsP8 : DecGemmArgs {
+    const float* wscale;   // fp32 [16 * ceil(N / 16)]: 2^e per output row
+};
+template <int NW, int MT, int EPI, int SPU, int UMAX = 0, bool P8 = false>
+__global__ __launch_bounds__(NW * 64) void gemv_rx_kernel(
+    typename std::conditional<P8, DecGemmArgsP8, DecGemmArgs>::type a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;   // [umax][MT][NW][64]
     const int nb = (int)gridDim.x, bu = (int)blockIdx.x;
@@ -218,23 +228,39 @@ __global__ __launch_bounds__(NW * 64) void gemv_rx_kernel(DecGemmArgs a) {
     const int kb_lo = (int)blockIdx.y * per;
     const int KBs = max(0, min(KB, kb_lo + per) - kb_lo);
     const int xr = lane & 15;
-    const __amdgpu_buffer_rsrc_t wr = frag_rsrc(a.W, (uint32_t)a.NG * (uint32_t)KB * 1024u);
-    auto wbatch = [&](int i, bf16x8_s(&w)[SPU]) __attribute__((always_inline)) {
+    // P8: the image has ceil(N / 16) groups; the padded groups of a.NG read zeros past it
+    const __amdgpu_buffer_rsrc_t wr =
+        P8 ? frag_rsrc(a.W, (uint32_t)p8_groups(a.N) * (uint32_t)KB * 512u)
+           : frag_rsrc(a.W, (uint32_t)a.NG * (uint32_t)KB * 1024u);
+    // a unit's weight batch as loaded: P16 fragments, or P8 fragments and the lane's row scale
+    using Frag = typename std::conditional<P8, u32x2, bf16x8_s>::type;
+    auto wbatch = [&](int i, Frag(&w)[SPU], float& s) __attribute__((always_inline)) {
         const int g = bu + i * nb;
 #pragma unroll
         for (int j = 0; j < SPU; ++j) {
             const int kb = wave + j * NW;
-            const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 16 : (int)0xfffffff0u;
-            w[j] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, 2));
+            if constexpr (P8) {
+                const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 8 : (int)0xfffffff0u;
+                w[j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(wr, off, 0, 2));
+            } else {
+                const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 16 : (int)0xfffffff0u;
+                w[j] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, 2));
+            }
+        }
+        if constexpr (P8) {
+            const __amdgpu_buffer_rsrc_t sr = frag_rsrc(a.wscale, (uint32_t)p8_groups(a.N) * 64u);
+            const int off = i < nu ? (g * 16 + xr) * 4 : (int)0xfffffff0u;
+            s = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(sr, off, 0, 0));
         }
     };
-    bf16x8_s wa[SPU], wb[SPU];
-    bf16x8_s wall[UMAX > 0 ? UMAX : 1][SPU];
+    Frag wa[SPU], wb[SPU];
+    Frag wall[UMAX > 0 ? UMAX : 1][SPU];
+    float sa = 0.f, sb = 0.f, sall[UMAX > 0 ? UMAX : 1] = {};   // P8 only
     if constexpr (UMAX > 0) {
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i) wbatch(i, wall[i]);
+        for (int i = 0; i < UMAX; ++i) wbatch(i, wall[i], sall[i]);
     } else {
-        wbatch(0, wa);
+        wbatch(0, wa, sa);
     }
     // this wave's X fragments (rows >= M and k-steps past the slice are zero)
     bf16x8_s xf[MT][SPU];
@@ -250,24 +276,32 @@ __global__ __launch_bounds__(NW * 64) void gemv_rx_kernel(DecGemmArgs a) {
             xf[t][j] = (row < a.M && wave + j * NW < KBs) ? v : z8;
         }
     }
-    auto mul = [&](int i, bf16x8_s(&w)[SPU]) __attribute__((always_inline)) {
+    auto mul = [&](int i, Frag(&w)[SPU], float s) __attribute__((always_inline)) {
+        bf16x8_s c[P8 ? SPU : 1];   // P8: the MFMA A operands, converted once per unit (not per tile)
+        if constexpr (P8) {
+#pragma unroll
+            for (int j = 0; j < SPU; ++j) c[j] = p8_to_bf16(w[j], s);
+        }
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < SPU; ++j) acc = mfma16(w[j], xf[t][j], acc);
+            for (int j = 0; j < SPU; ++j) {
+                if constexpr (P8) acc = mfma16(c[j], xf[t][j], acc);
+                else acc = mfma16(w[j], xf[t][j], acc);
+            }
             if (i < nu) red[((i * MT + t) * NW + wave) * 64 + lane] = acc;
         }
     };
     if constexpr (UMAX > 0) {
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i) mul(i, wall[i]);   // units past nu: zero batches, results dropped
+        for (int i = 0; i < UMAX; ++i) mul(i, wall[i], sall[i]);   // units past nu: zero batches, results dropped
     } else {
         for (int i = 0; i < nu; i += 2) {
-            wbatch(i + 1, wb);
-            mul(i, wa);
-            wbatch(i + 2, wa);
-            mul(i + 1, wb);
+            wbatch(i + 1, wb, sb);
+            mul(i, wa, sa);
+            wbatch(i + 2, wa, sa);
+            mul(i + 1, wb, sb);
         }
     }
     __syncthreads();
@@ -384,8 +418,9 @@ size_t gemv_dec_lds_bytes(const DecGemmArgs& a, int rg) {
 // 18 / 32: the attention projections' slices), SPU =
 // PER / NW per wave -- 0 if launched. Split-K launches put cu_count / splits blocks on each
 // slice, so every block streams several units against one register-held X slice.
-template <int NW, int MT, int EPI, int PER>
-static int launch_rx_nw(const DecGemmArgs& a, hipStream_t st) {
+// P8: the same launch (grid, LDS, UMAX rule) on an FP8 image with the row scales ws (fp8.h)
+template <int NW, int MT, int EPI, int PER, bool P8>
+static int launch_rx_nw(const DecGemmArgs& a, const float* ws, hipStream_t st) {
     static_assert(PER % NW == 0, "whole k-step batches per wave");
     constexpr int SPU = PER / NW;
     const int cap = a.max_grid > 0 ? a.max_grid : cu_count();
@@ -396,10 +431,10 @@ static int launch_rx_nw(const DecGemmArgs& a, hipStream_t st) {
     // un = -1 (tuning): the whole per-block weight stream requested up front, for blocks of
     // <= 5 units whose batches fit the register budget (SPU * 5 fragments per wave)
     bool all = false;
-    auto* fn = gemv_rx_kernel<NW, MT, EPI, SPU, 0>;
+    auto* fn = gemv_rx_kernel<NW, MT, EPI, SPU, 0, P8>;
     if constexpr (MT == 1 && SPU <= 6) {
         all = a.un == -1 && umax <= 5;
-        if (all) fn = gemv_rx_kernel<NW, MT, EPI, SPU, 5>;
+        if (all) fn = gemv_rx_kernel<NW, MT, EPI, SPU, 5, P8>;
     }
     static bool attr[T5G_MAX_DEVICES][2] = {};
     const int dev = t5g_cur_device();
@@ -407,35 +442,43 @@ static int launch_rx_nw(const DecGemmArgs& a, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GD_LDS_MAX);
         attr[dev][all] = true;
     }
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid, (unsigned)a.splits), dim3(NW * 64), shm, st, a);
+    if constexpr (P8) {
+        DecGemmArgsP8 a8;
+        static_cast<DecGemmArgs&>(a8) = a;
+        a8.wscale = ws;
+        hipLaunchKernelGGL(fn, dim3((unsigned)grid, (unsigned)a.splits), dim3(NW * 64), shm, st, a8);
+    } else {
+        hipLaunchKernelGGL(fn, dim3((unsigned)grid, (unsigned)a.splits), dim3(NW * 64), shm, st, a);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 // a.nw picks the waves sharing each unit's K stream (the PER k-steps split evenly; the
 // decode gate/up runs 12: 17.9 vs 18.5 us for 8 at 8 rows, tools/probe_rx_nw.py)
-template <int MT, int EPI, int PER>
-static int launch_rx(const DecGemmArgs& a, hipStream_t st) {
+template <int MT, int EPI, int PER, bool P8>
+static int launch_rx(const DecGemmArgs& a, const float* ws, hipStream_t st) {
     switch (a.nw) {
-        case 4: if constexpr (PER % 4 == 0) return launch_rx_nw<4, MT, EPI, PER>(a, st); else return -1;
-        case 6: if constexpr (PER % 6 == 0) return launch_rx_nw<6, MT, EPI, PER>(a, st); else return -1;
-        case 9: if constexpr (PER % 9 == 0) return launch_rx_nw<9, MT, EPI, PER>(a, st); else return -1;
-        case 12: if constexpr (PER % 12 == 0) return launch_rx_nw<12, MT, EPI, PER>(a, st); else return -1;
-        case 8: if constexpr (PER % 8 == 0) return launch_rx_nw<8, MT, EPI, PER>(a, st); else return -1;
+        case 4: if constexpr (PER % 4 == 0) return launch_rx_nw<4, MT, EPI, PER, P8>(a, ws, st); else return -1;
+        case 6: if constexpr (PER % 6 == 0) return launch_rx_nw<6, MT, EPI, PER, P8>(a, ws, st); else return -1;
+        case 9: if constexpr (PER % 9 == 0) return launch_rx_nw<9, MT, EPI, PER, P8>(a, ws, st); else return -1;
+        case 12: if constexpr (PER % 12 == 0) return launch_rx_nw<12, MT, EPI, PER, P8>(a, ws, st); else return -1;
+        case 8: if constexpr (PER % 8 == 0) return launch_rx_nw<8, MT, EPI, PER, P8>(a, ws, st); else return -1;
         default: return -1;   // a wave split the kernel is not built for (a different sum order)
     }
 }
-template <int MT>
-static int launch_rx_slabs(const DecGemmArgs& a, int per, hipStream_t st) {
+template <int MT, bool P8>
+static int launch_rx_slabs(const DecGemmArgs& a, const float* ws, int per, hipStream_t st) {
     switch (per) {
-        case 8: return launch_rx<MT, EPI_F32, 8>(a, st);
-        case 16: return launch_rx<MT, EPI_F32, 16>(a, st);
-        case 18: return launch_rx<MT, EPI_F32, 18>(a, st);
-        case 32: return launch_rx<MT, EPI_F32, 32>(a, st);
-        case 36: return launch_rx<MT, EPI_F32, 36>(a, st);
+        case 8: return launch_rx<MT, EPI_F32, 8, P8>(a, ws, st);
+        case 16: return launch_rx<MT, EPI_F32, 16, P8>(a, ws, st);
+        case 18: return launch_rx<MT, EPI_F32, 18, P8>(a, ws, st);
+        case 32: return launch_rx<MT, EPI_F32, 32, P8>(a, ws, st);
+        case 36: return launch_rx<MT, EPI_F32, 36, P8>(a, ws, st);
         default: return -1;
     }
 }
 
-int gemv_rx(const DecGemmArgs& a, int epi, hipStream_t st) {
+template <bool P8>
+static int gemv_rx_t(const DecGemmArgs& a, const float* ws, int epi, hipStream_t st) {
     if (a.M <= 0 || a.M > 32 || a.K != a.KB * 32 || a.NG % 4 || a.NG * 16 < a.N) return -1;
     if (a.splits < 1 || a.KB % a.splits) return -1;
     const int per = a.KB / a.splits;
@@ -446,13 +489,21 @@ int gemv_rx(const DecGemmArgs& a, int epi, hipStream_t st) {
     if ((epi == EPI_BIAS_BF16 || epi == EPI_BIAS_GELU) && !a.bias) return -1;
     const bool two = a.M > 16;
     switch (epi) {
-        case EPI_BF16: return two ? launch_rx<2, EPI_BF16, 72>(a, st) : launch_rx<1, EPI_BF16, 72>(a, st);
-        case EPI_BIAS_BF16: return two ? launch_rx<2, EPI_BIAS_BF16, 72>(a, st) : launch_rx<1, EPI_BIAS_BF16, 72>(a, st);
-        case EPI_BIAS_GELU: return two ? launch_rx<2, EPI_BIAS_GELU, 72>(a, st) : launch_rx<1, EPI_BIAS_GELU, 72>(a, st);
-        case EPI_GEGLU: return two ? launch_rx<2, EPI_GEGLU, 72>(a, st) : launch_rx<1, EPI_GEGLU, 72>(a, st);
-        case EPI_F32: return two ? launch_rx_slabs<2>(a, per, st) : launch_rx_slabs<1>(a, per, st);
+        case EPI_BF16: return two ? launch_rx<2, EPI_BF16, 72, P8>(a, ws, st) : launch_rx<1, EPI_BF16, 72, P8>(a, ws, st);
+        case EPI_BIAS_BF16: return two ? launch_rx<2, EPI_BIAS_BF16, 72, P8>(a, ws, st) : launch_rx<1, EPI_BIAS_BF16, 72, P8>(a, ws, st);
+        case EPI_BIAS_GELU: return two ? launch_rx<2, EPI_BIAS_GELU, 72, P8>(a, ws, st) : launch_rx<1, EPI_BIAS_GELU, 72, P8>(a, ws, st);
+        case EPI_GEGLU: return two ? launch_rx<2, EPI_GEGLU, 72, P8>(a, ws, st) : launch_rx<1, EPI_GEGLU, 72, P8>(a, ws, st);
+        case EPI_F32: return two ? launch_rx_slabs<2, P8>(a, ws, per, st) : launch_rx_slabs<1, P8>(a, ws, per, st);
         default: return -1;
     }
+}
+
+int gemv_rx(const DecGemmArgs& a, int epi, hipStream_t st) { return gemv_rx_t<false>(a, nullptr, epi, st); }
+
+int gemv_rx_p8(const DecGemmArgs& a, const float* wscale, int epi, hipStream_t st) {
+    if (a.M <= 0) return 0;
+    if (!a.layout_rx || !a.W || !wscale) return -1;
+    return gemv_rx_t<true>(a, wscale, epi, st);
 }
 
 int gemv_dec(const DecGemmArgs& a, int epi, hipStream_t st) {

@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from .config import VoiceConfig
 from .noise import DeviceNoise
-from .weights import check_state_dict
+from .weights import WEIGHT_FORMATS, check_state_dict, fp8_supported
 
 BF16 = torch.bfloat16
 MAX_AUDIO = 12288   # cache capacity of both kernel sets: 24 aten kv blocks of 512 keys (t5g_kernels.h)
@@ -89,9 +89,23 @@ class T5GemmaTTSEngine:
 
     def __init__(self, cfg: VoiceConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0",
                  max_batch: int = 8, max_text: int = 128, max_audio: int = 1024, max_gen: Optional[int] = None,
-                 free_source: bool = False, shared_from: Optional["T5GemmaTTSEngine"] = None):
+                 free_source: bool = False, shared_from: Optional["T5GemmaTTSEngine"] = None,
+                 weight_format: str = "bf16"):
         """``shared_from``: reuse another engine's packed weights on the same device (e.g. a
-        second KV arena / batch slot set without a second 10.6 GB weight copy)."""
+        second KV arena / batch slot set without a second 10.6 GB weight copy); it must have
+        the same ``weight_format``.
+        ``weight_format="fp8"`` (opt-in, fast path only): the weights a decode step streams --
+        ``weights.fp8_quantized_names`` -- are quantised at load to FP8 e4m3 with power-of-two
+        row scales (csrc/fp8.hip) and the decode step's GEMVs and head stream those; every
+        other phase reads the bf16 image of the same rounded weights W_q. Logits are bitwise
+        those of a bf16 engine built from ``weights.fp8_rounded_state_dict(cfg, sd)``; parity
+        mode is refused. Needs the 2b-2b widths (``weights.fp8_supported``)."""
+        if weight_format not in WEIGHT_FORMATS:
+            raise ValueError(f"weight_format {weight_format!r}: one of {WEIGHT_FORMATS}")
+        if weight_format == "fp8" and not fp8_supported(cfg):
+            raise ValueError("weight_format='fp8' needs hidden 2304, intermediate 9216, q_dim 2048 (the widths the "
+                             "decode step's register-X GEMVs are built for)")
+        self.weight_format = weight_format
         if not torch.cuda.is_available():
             raise RuntimeError("T5GemmaTTSEngine needs a ROCm GPU (MI355X); there is no CPU fallback")
         self.L = _lib.lib()
@@ -108,8 +122,11 @@ class T5GemmaTTSEngine:
         if shared_from is not None:
             if shared_from.device != dev or shared_from.cfg != cfg:
                 raise ValueError("shared_from must be an engine of the same config on the same device")
+            if shared_from.weight_format != weight_format:
+                raise ValueError(f"shared_from holds {shared_from.weight_format} weights, not {weight_format}")
             self._keep = shared_from._keep
             self._enc, self._dec, self._weights = shared_from._enc, shared_from._dec, shared_from._weights
+            self._fp8 = shared_from._fp8
             self._create(cfg, shared_from._weights)
             return
         check_state_dict(cfg, state_dict)
@@ -134,6 +151,26 @@ class T5GemmaTTSEngine:
             _lib.check(self.L.t5g_pack_weight(_ptr(mat), N, K, K, _ptr(dst), stream), "pack")
             return keep(dst)
 
+        fp8 = weight_format == "fp8"
+
+        def pack8(mat: torch.Tensor, slot: _lib.Fp8Linear) -> int:
+            """FP8 mode, a Linear of the decode step: its P8 image + row scales into ``slot``,
+            and the P16 image of the dequantised W_q (returned) for the bf16 phases."""
+            if not fp8:
+                return pack(mat)
+            N, K = mat.shape
+            p8 = torch.empty(self.L.t5g_fp8_packed_bytes(N, K), dtype=torch.uint8, device=dev)
+            scale = torch.empty(-(-N // 16) * 16, dtype=torch.float32, device=dev)
+            wq = torch.empty(N, K, dtype=BF16, device=dev)
+            _lib.check(self.L.t5g_quantize_weight_fp8(_ptr(mat), N, K, K, _ptr(p8), _ptr(scale), _ptr(wq), stream),
+                       "quantize_weight_fp8 (non-finite weight?)")
+            slot.p8, slot.scale = keep(p8), keep(scale)
+            return pack(wq)
+
+        self._fp8 = None
+        dec8 = (_lib.Fp8Layer * bb.num_decoder_layers)()
+        head2_8 = _lib.Fp8Linear()
+
         d, f = bb.hidden_size, bb.intermediate_size
 
         def interleave_gate_up(gate, up):
@@ -144,21 +181,26 @@ class T5GemmaTTSEngine:
         def layer(side: str, i: int) -> _lib.LayerWeights:
             p = f"backbone.model.{side}.layers.{i}"
             lw = _lib.LayerWeights()
-            lw.qkv = pack(torch.cat([w(f"{p}.self_attn.q_proj.weight"), w(f"{p}.self_attn.k_proj.weight"),
-                                     w(f"{p}.self_attn.v_proj.weight")], 0))
-            lw.o = pack(w(f"{p}.self_attn.o_proj.weight"))
-            lw.gate_up = pack(interleave_gate_up(w(f"{p}.mlp.gate_proj.weight"), w(f"{p}.mlp.up_proj.weight")))
-            lw.down = pack(w(f"{p}.mlp.down_proj.weight"))
+            # FP8 mode quantises the decoder layers' decode-step Linears (row scales: the q|k|v
+            # concatenation and the gate/up interleave do not change a row's codes)
+            l8 = dec8[i] if side == "decoder" else None
+            pk = (lambda m, name: pack8(m, getattr(l8, name))) if l8 is not None else (lambda m, name: pack(m))
+            lw.qkv = pk(torch.cat([w(f"{p}.self_attn.q_proj.weight"), w(f"{p}.self_attn.k_proj.weight"),
+                                   w(f"{p}.self_attn.v_proj.weight")], 0), "qkv")
+            lw.o = pk(w(f"{p}.self_attn.o_proj.weight"), "o")
+            lw.gate_up = pk(interleave_gate_up(w(f"{p}.mlp.gate_proj.weight"), w(f"{p}.mlp.up_proj.weight")),
+                            "gate_up")
+            lw.down = pk(w(f"{p}.mlp.down_proj.weight"), "down")
             names = ["pre_self_attn_layernorm", "post_self_attn_layernorm", "pre_cross_attn_layernorm",
                      "post_cross_attn_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm"]
             for j, nm in enumerate(names):
                 key = f"{p}.{nm}.weight"
                 lw.norms[j] = keep(w(key)) if key in state_dict else None
             if side == "decoder":
-                lw.cross_q = pack(w(f"{p}.cross_attn.q_proj.weight"))
+                lw.cross_q = pk(w(f"{p}.cross_attn.q_proj.weight"), "cross_q")
                 lw.cross_kv = pack(torch.cat([w(f"{p}.cross_attn.k_proj.weight"),
                                               w(f"{p}.cross_attn.v_proj.weight")], 0))
-                lw.cross_o = pack(w(f"{p}.cross_attn.o_proj.weight"))
+                lw.cross_o = pk(w(f"{p}.cross_attn.o_proj.weight"), "cross_o")
             return lw
 
         self._enc = (_lib.LayerWeights * bb.num_encoder_layers)(
@@ -172,13 +214,18 @@ class T5GemmaTTSEngine:
         W.dec_final_norm = keep(w("backbone.model.decoder.norm.weight"))
         W.head1 = pack(w("predict_layer.0.0.weight"))
         W.head1_bias = keep(w("predict_layer.0.0.bias"))
-        W.head2 = pack(w("predict_layer.0.2.weight"))
+        W.head2 = pack8(w("predict_layer.0.2.weight"), head2_8)
         W.head2_bias = keep(w("predict_layer.0.2.bias"))
         inv = 1.0 / (bb.rope_theta ** (torch.arange(0, bb.head_dim, 2, dtype=torch.float) / bb.head_dim))
         W.inv_freq = keep(inv.to(dev))
         W.enc_layers = self._enc
         W.dec_layers = self._dec
         self._weights = W
+        if fp8:
+            W8 = _lib.Fp8Weights()
+            W8.dec_layers = dec8
+            W8.head2 = head2_8
+            self._fp8 = (W8, dec8)
         if free_source:
             state_dict.clear()
         self._create(cfg, W)
@@ -212,6 +259,11 @@ class T5GemmaTTSEngine:
         h = C.c_void_p()
         _lib.check(self.L.t5g_engine_create(C.byref(c), C.byref(W), C.byref(h)), "engine_create")
         self.h = h
+        if self._fp8 is not None:
+            rc = self.L.t5g_engine_set_fp8_weights(h, C.byref(self._fp8[0]))
+            if rc == _lib.T5G_EUNSUPPORTED:
+                raise ValueError("weight_format='fp8': config not supported by the FP8 decode kernels")
+            _lib.check(rc, "set_fp8_weights")
         ld = C.c_int32()
         self._logits_ptr = self.L.t5g_logits_ptr(h, C.byref(ld))
         self.logits_ld = ld.value
@@ -277,6 +329,12 @@ class T5GemmaTTSEngine:
         parity mode is unaffected (csrc/attn.hip)."""
         _lib.check(self.L.t5g_engine_set_attn_flash(self.h, 1 if enable else 0), "set_attn_flash")
 
+    def native_weight_format(self) -> str:
+        """The format the native engine reports (t5g_engine_weight_format): "bf16" or "fp8"."""
+        f = C.c_int32()
+        _lib.check(self.L.t5g_engine_weight_format(self.h, C.byref(f)), "weight_format")
+        return WEIGHT_FORMATS[f.value]
+
     def close(self):
         if getattr(self, "h", None):
             self.L.t5g_engine_destroy(self.h)
@@ -317,6 +375,9 @@ class T5GemmaTTSEngine:
         reference host's CPU order) or back to the fast kernels."""
         if bool(enable) == getattr(self, "_exact", False):
             return
+        if enable and self.weight_format == "fp8":
+            raise ValueError("weight_format='fp8' is fast path only: parity mode reproduces the reference's bf16 "
+                             "weights (generate(parity=False), or parity=True with exact=False for the host loop)")
         tab = _lib.gelu_erf_table() if enable else None
         if enable and self.cfg.backbone.softcap != 0.0 and not getattr(self, "_tanh_set", False):
             # eager attention: the reference host's bf16 tanh (csrc/eager.hip)
@@ -631,7 +692,8 @@ class T5GemmaVoiceForConditionalGeneration:
 
     ``from_pretrained(model_dir)`` reads the HF export (config.json +
     safetensors, no pickle); ``inference_tts`` keeps the reference signature
-    and return shapes (:565-862)."""
+    and return shapes (:565-862). ``weight_format="fp8"`` (also through ``from_pretrained``)
+    is passed to the engine: FP8 e4m3 decode weights, fast path only."""
 
     def __init__(self, cfg: VoiceConfig, state_dict, device="cuda:0", **engine_kw):
         self.config = cfg
@@ -666,8 +728,10 @@ class T5GemmaVoiceForConditionalGeneration:
         if parity is None:
             # the drop-in default: token-exact parity where it is restated (sdpa attention);
             # an eager / softcap checkpoint runs the fast kernels, and says so once
-            parity = _lib.eager_restated(cfg.backbone)
-            if not parity and not getattr(self, "_warned_eager", False):
+            parity = _lib.eager_restated(cfg.backbone) and self.engine.weight_format != "fp8"
+            if self.engine.weight_format == "fp8":
+                pass   # FP8 weights: fast path only, by the caller's choice of format
+            elif not parity and not getattr(self, "_warned_eager", False):
                 import warnings
                 warnings.warn("eager (softcap) attention checkpoint of an unmeasured shape: inference_tts runs the "
                               "fast kernels (logits within tolerance of the reference, tokens may differ); the "

@@ -129,3 +129,63 @@ def check_state_dict(cfg: VoiceConfig, sd: Dict[str, torch.Tensor]) -> None:
             raise ValueError(f"missing weight {name}")
         if tuple(sd[name].shape) != tuple(shape):
             raise ValueError(f"{name}: shape {tuple(sd[name].shape)} != {shape}")
+
+
+# ---- FP8 e4m3 weights for the fast decode step (opt-in; csrc/fp8.hip) ----
+WEIGHT_FORMATS = ("bf16", "fp8")
+FP8_MAX = 448.0      # largest finite e4m3fn magnitude
+FP8_EMIN = -100      # smallest row exponent: 2^-100 * 2^-9 (the smallest code) is a normal bf16
+
+
+def fp8_supported(cfg: VoiceConfig) -> bool:
+    """Whether an engine of this config takes ``weight_format="fp8"``: the widths the decode
+    step's register-X GEMV sites are built for (hidden 2304, intermediate 9216, q_dim 2048)."""
+    bb = cfg.backbone
+    return bb.hidden_size == 2304 and bb.intermediate_size == 9216 and bb.q_dim == 2048
+
+
+def fp8_quantized_names(cfg: VoiceConfig) -> List[str]:
+    """State-dict keys of the tensors FP8 mode quantises -- what a decode step streams: every
+    DECODER layer's self q / k / v / o, cross q / o, gate / up / down projections, and the
+    65 541-row head ``predict_layer.0.2``. Not the encoder, the cross k / v projections (once
+    per call), ``predict_layer.0.0``, embeddings, norms or biases."""
+    names = []
+    for i in range(cfg.backbone.num_decoder_layers):
+        p = f"{DEC}.layers.{i}"
+        names += [f"{p}.self_attn.{n}_proj.weight" for n in "qkvo"]
+        names += [f"{p}.cross_attn.q_proj.weight", f"{p}.cross_attn.o_proj.weight"]
+        names += [f"{p}.mlp.{n}_proj.weight" for n in ("gate", "up", "down")]
+    return names + ["predict_layer.0.2.weight"]
+
+
+def quantize_fp8_rows(W: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The quantiser rule of csrc/fp8.hip restated in torch, per output row of ``W`` [N][K]
+    (taken as bf16): ``e`` = the smallest integer >= -100 with ``amax * 2^-e <= 448`` (0 for an
+    all-zero row), ``q = RNE_e4m3fn(W * 2^-e)`` (the scaling is exact; the NaN codes 0x7F / 0xFF
+    are never produced). Returns ``(codes uint8 [N][K], scale fp32 [N] = 2^e, Wq bf16 [N][K])``
+    with ``Wq = 2^e * q`` exactly. A non-finite weight raises ValueError."""
+    if W.dim() != 2:
+        raise ValueError(f"quantize_fp8_rows takes an [N][K] matrix, got {tuple(W.shape)}")
+    w = W.detach().to(torch.bfloat16).float().cpu()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_fp8_rows: non-finite weight")
+    amax = w.abs().amax(dim=1)
+    fr, ex = torch.frexp(amax)                       # amax = fr * 2^ex, fr in [0.5, 1); 448 = 0.875 * 2^9
+    e = torch.where(fr <= 0.875, ex - 9, ex - 8).clamp(min=FP8_EMIN)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).to(torch.int32)
+    q8 = torch.ldexp(w, (-e)[:, None]).to(torch.float8_e4m3fn)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    wq = torch.ldexp(q8.float(), e[:, None])
+    assert bool((wq.bfloat16().float() == wq).all()), "2^e * q must be exactly bf16"
+    return q8.view(torch.uint8), scale, wq.bfloat16()
+
+
+def fp8_rounded_state_dict(cfg: VoiceConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """``sd`` with exactly the tensors FP8 mode quantises (``fp8_quantized_names``) replaced by
+    their dequantised images W_q: an ordinary bf16 engine built from it computes, bit for bit,
+    what a ``weight_format="fp8"`` engine built from ``sd`` computes on the fast path."""
+    out = dict(sd)
+    for name in fp8_quantized_names(cfg):
+        t = sd[name]
+        out[name] = quantize_fp8_rows(t)[2].to(device=t.device, dtype=t.dtype)
+    return out

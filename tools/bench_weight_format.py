@@ -1,0 +1,105 @@
+"""A/B of the decode weight formats on bench.py's C3 workload (8 rows, T_x 60, T_p 151, 751
+tokens per row): one process, one session, the arms interleaved round after round --
+
+    bf16          the default engine (whole-layer launches)
+    fp8           weight_format="fp8" (per-op launches on the P8 GEMVs, P8 head)
+    bf16_per_op   the default engine after set_fused(False): the same launches as fp8, on bf16
+
+each ``--steps`` timed generate() calls after ``--warmup`` untimed ones, as bench.py times
+them (the workload definitions are bench.py's own, imported). One JSON line per run goes to
+``--out`` (default profiles/r09_fp8_c3_ab.jsonl), then a summary line: tok/s per run, the
+within-arm spread over the rounds, and the device time of one decode step (t5g_time_decode_step)
+per arm. The baseline of any statement about fp8 is the bf16 runs of the same file.
+
+    python tools/bench_weight_format.py --rounds 2 --steps 20 --warmup 5
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import bench  # noqa: E402  (WORKLOADS, request_rows, request_seed, DUR_FRAMES)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="c3")
+    ap.add_argument("--time-iters", type=int, default=200, help="decode steps timed by t5g_time_decode_step")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r09_fp8_c3_ab.jsonl"))
+    args = ap.parse_args()
+
+    import torch
+
+    from t5gemma_tts_amd import _lib
+    from t5gemma_tts_amd.config import config_2b2b
+    from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance
+    from t5gemma_tts_amd.weights import synthetic_weights
+
+    B, T_x, T_p, _, _ = bench.WORKLOADS[args.workload]
+    dev = "cuda:0"
+    cfg = config_2b2b()
+    torch.manual_seed(1234)
+    sd = synthetic_weights(cfg, seed=1234, device=dev)
+    n_tok_row = bench.DUR_FRAMES + int(cfg.extra_budget) + 1
+    kw = dict(device=dev, max_batch=B, max_text=128, max_audio=T_p + 1 + n_tok_row + 8, max_gen=n_tok_row + 4)
+    engines = {"bf16": T5GemmaTTSEngine(cfg, sd, **kw), "fp8": T5GemmaTTSEngine(cfg, sd, weight_format="fp8", **kw)}
+    rows = bench.request_rows(cfg, B, T_x, T_p)
+    utts = [Utterance(x=r[3:3 + r[0]], y=r[3 + r[0]:], tgt_y_len=r[1]) for r in rows]
+    params = SamplingParams(top_k=30, top_p=0.9, temperature=0.8, stop_repetition=3, eos_disabled=True)
+    arms = ["bf16", "fp8", "bf16_per_op"]
+
+    def run(arm: str, rnd: int) -> dict:
+        eng = engines["fp8" if arm == "fp8" else "bf16"]
+        eng.set_fused(arm != "bf16_per_op")
+        step = lambda i: sum(len(g) for g in eng.generate(   # noqa: E731
+            utts, params, seeds=[bench.request_seed(i, r[2]) for r in rows], chunk=64)["gen"])
+        for i in range(args.warmup):
+            step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tokens = sum(step(100 + i) for i in range(args.steps))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        # device time of one decode step (sampler excluded) at the cache lengths the call left
+        us = C.c_float()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(eng.L.t5g_time_decode_step(eng.h, args.time_iters, stream, C.byref(us)), "time_decode_step")
+        eng.set_fused(True)
+        return {"arm": arm, "round": rnd, "workload": args.workload, "steps": args.steps, "warmup": args.warmup,
+                "tokens": tokens, "seconds": round(dt, 4), "tok_s": round(tokens / dt, 1),
+                "decode_step_us": round(us.value, 1), "weight_format": eng.native_weight_format(),
+                "block_launches": eng.block_launches(), "device": torch.cuda.get_device_name(0)}
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    runs = []
+    with open(args.out, "w") as f:
+        for rnd in range(args.rounds):
+            for arm in arms:
+                r = run(arm, rnd)
+                runs.append(r)
+                f.write(json.dumps(r) + "\n")
+                f.flush()
+                print(json.dumps(r), flush=True)
+        summary = {"summary": True, "weights": "synthetic (seed 1234)"}
+        for arm in arms:
+            v = [r["tok_s"] for r in runs if r["arm"] == arm]
+            u = [r["decode_step_us"] for r in runs if r["arm"] == arm]
+            summary[arm] = {"tok_s": v, "spread_pct": round(100 * (max(v) - min(v)) / min(v), 2),
+                            "decode_step_us": u}
+        mean = lambda arm: sum(summary[arm]["tok_s"]) / len(summary[arm]["tok_s"])   # noqa: E731
+        summary["fp8_vs_bf16"] = round(mean("fp8") / mean("bf16"), 4)
+        summary["fp8_vs_bf16_per_op"] = round(mean("fp8") / mean("bf16_per_op"), 4)
+        f.write(json.dumps(summary) + "\n")
+        print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    main()
