@@ -329,6 +329,94 @@ int t5g_resid_norm(int32_t M, int32_t d, const void* delta, const void* resid, c
 int t5g_time_gemv(const t5g_gemv_args* args, const void* const* Wp_list, int32_t n_w, int32_t iters, void* stream,
                   float* avg_us);
 
+/* The fast path's encoder / prefill kernels on caller buffers, for kernel-level tests. Each
+ * hook fills the launch arguments the engine's own call sites fill and calls the same host
+ * launcher; every argument is checked on the host before anything is launched.
+ *
+ * Many-query attention (csrc/attn.hip attn_kernel through attention(): encoder self attention
+ * with a bidirectional window, [tf] T5GemmaEncoderLayer :393-442 under the masks of :765-786;
+ * decoder prefill self attention with a causal window, T5GemmaSelfAttention :264-304; prefill
+ * cross attention, PMCrossAttention :167-253): query i belongs to row q_row[i] (null: row i) at
+ * position q_pos[i] (null: the row's last key) and sees keys [0, min(t + 1, kv_len)) when
+ * causal (window W > 0: from t - W + 1), else [0, kv_len) (W > 0: |t - k| <= W). softcap > 0
+ * selects the eager numerics (bf16 scores, tanh softcap, bf16 normalised probabilities:
+ * eager_attention_forward modeling_t5gemma.py:199-230), else torch's CPU SDPA block order.
+ * One launch, cap score slots per q head in LDS: n_heads / n_kv_heads * cap * 4 bytes may
+ * not exceed 96 KiB (T5G_EINVAL); an unbuilt (head_dim, group) is T5G_EUNSUPPORTED. */
+typedef struct {
+    int32_t Mq, n_heads, n_kv_heads, head_dim;
+    const void* q;            /* bf16 [Mq][n_heads * head_dim], PM-RoPE already applied */
+    const int32_t* q_row;     /* device [Mq] or NULL */
+    const int32_t* q_pos;     /* device [Mq] or NULL */
+    const void* k_cache;      /* bf16 [B][n_kv_heads][cap][head_dim] */
+    const void* v_cache;
+    const int32_t* kv_len;    /* device [B] */
+    int32_t cap, causal, window;
+    float scale, softcap;
+    int32_t reserved;         /* must be 0 (T5G_EINVAL) */
+    void* out;                /* bf16 [Mq][n_heads * head_dim] */
+} t5g_attn_packed_args;
+int t5g_attention_packed(const t5g_attn_packed_args* args, void* stream);
+/* PM-RoPE + KV-cache store (csrc/attn.hip rope_store_kernel; [tf] T5GemmaRotaryEmbedding +
+ * apply_rotary_pos_emb on float progress positions, hf_export/modeling_t5gemma_voice.py
+ * :516-531, 669-681, 817-832, and the cache update of cache_utils.py:127-144): token m's row
+ * holds nq | nk | nv heads of D columns from column col0 -- bf16 X, or fp32 split-K slabs
+ * Xpart [nsplit][M][ldx] (nsplit 1..8) summed in slab order and rounded. q heads go to
+ * Qout[m] (rotated when rope_q; Qout may be X itself with ldq == ldx), k heads (rotated when
+ * rope_k) and v heads to slot tok_t[m] (null: kv_len[row] - 1) of row tok_row[m] (null: m)
+ * of the caches. cos / sin: bf16(cosf / sinf(inv_freq[i] * pos[m])), or rope_tab[row][D]
+ * (cos | sin) when given. The fast-mode trig only. */
+typedef struct {
+    const void* X;            /* bf16 [M][ldx], or NULL with Xpart */
+    const float* Xpart;       /* fp32 [nsplit][M][ldx], or NULL with X */
+    int32_t nsplit, ldx, M, D;
+    int32_t nq, nk, nv, col0;
+    int32_t rope_q, rope_k;
+    const float* pos;         /* device [M] */
+    const float* inv_freq;    /* device [D / 2] */
+    const int32_t* tok_row;   /* device [M] or NULL */
+    const int32_t* tok_t;     /* device [M] or NULL */
+    const int32_t* kv_len;    /* device [rows]; needed when tok_t is NULL */
+    void* Qout;               /* bf16 [M][ldq] (nq > 0) */
+    int32_t ldq, reserved;    /* reserved: must be 0 (T5G_EINVAL) */
+    void* Kc;                 /* bf16 cache, element strides c_bstride per row, c_hstride per head */
+    void* Vc;
+    int64_t c_bstride, c_hstride;
+    const float* rope_tab;    /* device [rows][D] or NULL */
+} t5g_rope_store_args;
+int t5g_rope_store(const t5g_rope_store_args* args, void* stream);
+/* t5g_resid_norm with the kernel's other two sources and side outputs (csrc/norm.hip; [tf]
+ * T5GemmaRMSNorm :61-78, the embedding x sqrt(d) of :789-790): v = delta, or
+ * bf16(table[ids[m]] * scale), or bf16(part[0] + part[1] + ...) over fp32 slabs
+ * [nsplit][M][ldp] (nsplit 1..8, ldp % 4 == 0) -- exactly one of the three. post_w, resid and
+ * pre_w may each be NULL (that stage is skipped; pre_w needs normed_out). out_rows (delta or
+ * ids source): only rows out_rows[i], i < M, written compact, resid read at the source row.
+ * rope_tab: row i's block also writes bf16(cos | sin)(rope_inv_freq * rope_pos[i]) into
+ * rope_tab[i][rope_D] (the decode step's table; no reference-side equivalent). d % 8 == 0,
+ * d <= 8192. The fast-mode sums only. */
+typedef struct {
+    int32_t M, d;
+    const void* delta;        /* bf16 [M][d] */
+    const int32_t* ids;       /* device [M] */
+    const void* table;        /* bf16 [n_table][d] */
+    int32_t n_table;
+    float scale;
+    const float* part;        /* fp32 [nsplit][M][ldp] */
+    int32_t nsplit, ldp;
+    const void* resid;        /* bf16 [M][d] (out_rows: [source rows][d]) */
+    const void* post_w;       /* bf16 [d] */
+    const void* pre_w;
+    float eps;
+    int32_t rope_D;
+    void* resid_out;          /* bf16 [M][d] or NULL */
+    void* normed_out;         /* bf16 [M][d] or NULL */
+    const int32_t* out_rows;  /* device [M] or NULL */
+    const float* rope_pos;    /* device [M] */
+    const float* rope_inv_freq;   /* device [rope_D / 2] */
+    float* rope_tab;          /* device [M][rope_D] or NULL */
+} t5g_norm_src_args;
+int t5g_resid_norm_src(const t5g_norm_src_args* args, void* stream);
+
 /* Decode attention on caller buffers (single-query rows, sdpa numerics): the kernels the
  * engine's decode step runs for self / cross attention ([tf] T5GemmaSelfAttention
  * :264-304 with the KV cache of cache_utils.py:127-144; PMCrossAttention :167-253) --

@@ -107,6 +107,32 @@ class AttnDecodeArgs(C.Structure):
                 ("out", C.c_void_p), ("work", C.c_void_p)]
 
 
+class AttnPackedArgs(C.Structure):
+    _fields_ = [("Mq", C.c_int32), ("n_heads", C.c_int32), ("n_kv_heads", C.c_int32), ("head_dim", C.c_int32),
+                ("q", C.c_void_p), ("q_row", C.c_void_p), ("q_pos", C.c_void_p), ("k_cache", C.c_void_p),
+                ("v_cache", C.c_void_p), ("kv_len", C.c_void_p), ("cap", C.c_int32), ("causal", C.c_int32),
+                ("window", C.c_int32), ("scale", C.c_float), ("softcap", C.c_float), ("reserved", C.c_int32),
+                ("out", C.c_void_p)]
+
+
+class RopeStoreArgs(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("Xpart", C.c_void_p), ("nsplit", C.c_int32), ("ldx", C.c_int32),
+                ("M", C.c_int32), ("D", C.c_int32), ("nq", C.c_int32), ("nk", C.c_int32), ("nv", C.c_int32),
+                ("col0", C.c_int32), ("rope_q", C.c_int32), ("rope_k", C.c_int32), ("pos", C.c_void_p),
+                ("inv_freq", C.c_void_p), ("tok_row", C.c_void_p), ("tok_t", C.c_void_p), ("kv_len", C.c_void_p),
+                ("Qout", C.c_void_p), ("ldq", C.c_int32), ("reserved", C.c_int32), ("Kc", C.c_void_p),
+                ("Vc", C.c_void_p), ("c_bstride", C.c_int64), ("c_hstride", C.c_int64), ("rope_tab", C.c_void_p)]
+
+
+class NormSrcArgs(C.Structure):
+    _fields_ = [("M", C.c_int32), ("d", C.c_int32), ("delta", C.c_void_p), ("ids", C.c_void_p),
+                ("table", C.c_void_p), ("n_table", C.c_int32), ("scale", C.c_float), ("part", C.c_void_p),
+                ("nsplit", C.c_int32), ("ldp", C.c_int32), ("resid", C.c_void_p), ("post_w", C.c_void_p),
+                ("pre_w", C.c_void_p), ("eps", C.c_float), ("rope_D", C.c_int32), ("resid_out", C.c_void_p),
+                ("normed_out", C.c_void_p), ("out_rows", C.c_void_p), ("rope_pos", C.c_void_p),
+                ("rope_inv_freq", C.c_void_p), ("rope_tab", C.c_void_p)]
+
+
 # name -> (restype, argtypes); exactly the functions include/t5gtts.h declares
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -141,6 +167,9 @@ SIGNATURES = {
     "t5g_sample_only": (C.c_int, [_P, _I, _P, _I, _P]),
     "t5g_gemm": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
     "t5g_resid_norm": (C.c_int, [_I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "t5g_resid_norm_src": (C.c_int, [C.POINTER(NormSrcArgs), _P]),
+    "t5g_rope_store": (C.c_int, [C.POINTER(RopeStoreArgs), _P]),
+    "t5g_attention_packed": (C.c_int, [C.POINTER(AttnPackedArgs), _P]),
     "t5g_time_gemm": (C.c_int, [_P, _I, _I, C.POINTER(_P), _I, _I, _I, _I, _P, _I, _I, _I, _P, C.POINTER(_F)]),
     "t5g_time_decode_step": (C.c_int, [_P, _I, _P, C.POINTER(_F)]),
     "t5g_gemv": (C.c_int, [C.POINTER(GemvArgs), _P]),
@@ -275,6 +304,7 @@ FUSED_BLOCK_S_KERNEL = ("fused_block_kernel<2> (decode layer in one launch with 
                         "at its end: norm -> cross-q -> PM cross attention -> cross-o -> norm -> gate/up GeGLU -> "
                         "down -> norm -> next q|k|v -> next layer's flash self attention over its cached K / V + "
                         "append -> next o-proj, 174.6 MB of weights)")
+T5G_EINVAL = -1
 T5G_EUNSUPPORTED = -3
 
 # kernel sources each PMC-measured op is built from: a profiles/*_pmc_*.json records their

@@ -1,6 +1,7 @@
 // Outside the product path: the hipEvent timing hooks (t5g_time_*; bench.py --full prices its
 // rooflines with them, tools/ probe with them) and the stand-alone op wrappers tests and probes
-// call (t5g_gemm, t5g_gemv, t5g_resid_norm, the attention and exact-order entry points, ...).
+// call (t5g_gemm, t5g_gemv, t5g_resid_norm(_src), t5g_rope_store, the attention and exact-order
+// entry points, ...).
 // The decode hooks launch what a decode step launches: they take the step's plan
 // (decode_plan, engine.hip) instead of deciding for themselves.
 #include <algorithm>
@@ -333,6 +334,130 @@ extern "C" int t5g_resid_norm(int32_t M, int32_t d, const void* delta, const voi
     n.resid_out = (bf16_t*)resid_out;
     n.normed_out = (bf16_t*)normed_out;
     RC(resid_norm(n, (hipStream_t)stream));
+    return T5G_OK;
+}
+
+static_assert(sizeof(t5g_norm_src_args) == 136, "t5g_norm_src_args layout");
+
+extern "C" int t5g_resid_norm_src(const t5g_norm_src_args* g, void* stream) {
+    if (!g || g->M <= 0 || g->d <= 0 || g->d % 8 || g->d > 8 * 1024) return T5G_EINVAL;
+    if ((g->delta != nullptr) + (g->ids != nullptr) + (g->part != nullptr) != 1) return T5G_EINVAL;
+    if (g->ids && (!g->table || g->n_table <= 0)) return T5G_EINVAL;
+    if (g->part && (g->nsplit < 1 || g->nsplit > 8 || g->ldp < g->d || g->ldp % 4)) return T5G_EINVAL;
+    if ((!g->resid_out && !g->normed_out) || (g->pre_w && !g->normed_out)) return T5G_EINVAL;
+    if (g->rope_tab && (!g->rope_pos || !g->rope_inv_freq || g->rope_D <= 0 || g->rope_D % 2)) return T5G_EINVAL;
+    // out_rows: the slabs' row stride is M (the compact count), and without resid or delta
+    // resid_norm()'s stand-in for the absent resid is a compact output buffer, which the kernel
+    // reads at the source row -- past its end. resid_norm() itself does not check this (its
+    // engine caller gathers with delta); a caller that adds another out_rows form must.
+    if (g->out_rows && g->part) return T5G_EUNSUPPORTED;
+    if (g->out_rows && !g->resid && !g->delta) return T5G_EINVAL;
+    NormArgs n = norm_args(g->M, g->d, g->eps);
+    n.delta = (const bf16_t*)g->delta;
+    n.ids = g->ids;
+    n.table = (const bf16_t*)g->table;
+    n.n_table = g->n_table;
+    n.scale = g->scale;
+    n.part = g->part;
+    n.nsplit = g->part ? g->nsplit : 0;
+    n.ldp = g->ldp;
+    n.resid = (const bf16_t*)g->resid;
+    n.post_w = (const bf16_t*)g->post_w;
+    n.pre_w = (const bf16_t*)g->pre_w;
+    n.resid_out = (bf16_t*)g->resid_out;
+    n.normed_out = (bf16_t*)g->normed_out;
+    n.out_rows = g->out_rows;
+    if (g->rope_tab) {
+        n.rope_pos = g->rope_pos;
+        n.rope_inv_freq = g->rope_inv_freq;
+        n.rope_tab = g->rope_tab;
+        n.rope_D = g->rope_D;
+    }
+    RC(resid_norm(n, (hipStream_t)stream));
+    return T5G_OK;
+}
+
+static_assert(sizeof(t5g_rope_store_args) == 152, "t5g_rope_store_args layout");
+
+extern "C" int t5g_rope_store(const t5g_rope_store_args* g, void* stream) {
+    if (!g || g->reserved || (g->X != nullptr) == (g->Xpart != nullptr)) return T5G_EINVAL;
+    if (g->M <= 0 || g->D <= 0 || g->D % 2 || g->nq < 0 || g->nk < 0 || g->nv < 0 || g->nq + g->nk + g->nv <= 0 ||
+        g->col0 < 0 || g->ldx < g->col0 + (g->nq + g->nk + g->nv) * g->D)
+        return T5G_EINVAL;
+    if (g->Xpart && (g->nsplit < 1 || g->nsplit > 8)) return T5G_EINVAL;
+    if (g->nq && (!g->Qout || g->ldq < g->nq * g->D)) return T5G_EINVAL;
+    if (g->nq && g->Qout == g->X && g->ldq != g->ldx) return T5G_EINVAL;
+    if ((g->nk && !g->Kc) || (g->nv && !g->Vc)) return T5G_EINVAL;
+    if (g->nk + g->nv > 0 && ((!g->tok_t && !g->kv_len) || g->c_hstride < g->D || g->c_bstride < 0)) return T5G_EINVAL;
+    const bool rot = (g->nq && g->rope_q) || (g->nk && g->rope_k);
+    if (rot && !g->rope_tab && (!g->pos || !g->inv_freq)) return T5G_EINVAL;
+    RopeArgs r;
+    memset(&r, 0, sizeof(r));
+    r.X = (const bf16_t*)g->X;
+    r.Xpart = g->Xpart;
+    r.nsplit = g->Xpart ? g->nsplit : 0;
+    r.ldx = g->ldx;
+    r.M = g->M;
+    r.D = g->D;
+    r.nq = g->nq;
+    r.nk = g->nk;
+    r.nv = g->nv;
+    r.col0 = g->col0;
+    r.rope_q = g->rope_q;
+    r.rope_k = g->rope_k;
+    r.pos = g->pos;
+    r.inv_freq = g->inv_freq;
+    r.tok_row = g->tok_row;
+    r.tok_t = g->tok_t;
+    r.kv_len = g->kv_len;
+    r.Qout = (bf16_t*)g->Qout;
+    r.ldq = g->ldq;
+    r.Kc = (bf16_t*)g->Kc;
+    r.Vc = (bf16_t*)g->Vc;
+    r.c_bstride = (long)g->c_bstride;
+    r.c_hstride = (long)g->c_hstride;
+    r.rope_tab = g->rope_tab;
+    RC(rope_store(r, (hipStream_t)stream));
+    return T5G_OK;
+}
+
+static_assert(sizeof(t5g_attn_packed_args) == 96, "t5g_attn_packed_args layout");
+
+extern "C" int t5g_attention_packed(const t5g_attn_packed_args* g, void* stream) {
+    if (!g || g->reserved || !g->q || !g->k_cache || !g->v_cache || !g->kv_len || !g->out) return T5G_EINVAL;
+    if (g->Mq <= 0 || g->n_kv_heads <= 0 || g->n_heads <= 0 || g->n_heads % g->n_kv_heads || g->head_dim <= 0 ||
+        g->cap <= 0 || g->window < 0 || g->softcap < 0.f)
+        return T5G_EINVAL;
+    const int G = g->n_heads / g->n_kv_heads;
+    // an unbuilt geometry is reported as such, whatever its score footprint would be
+    if (!((g->head_dim == 256 && (G == 1 || G == 2)) || (G == 2 && (g->head_dim == 64 || g->head_dim == 128))))
+        return T5G_EUNSUPPORTED;
+    if (g->cap > SDPA_KV_BLOCK * SDPA_MAX_BLOCKS || (size_t)G * g->cap * sizeof(float) > 96 * 1024) return T5G_EINVAL;
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Q = (const bf16_t*)g->q;
+    a.ldq = g->n_heads * g->head_dim;
+    a.Mq = g->Mq;
+    a.q_row = g->q_row;
+    a.q_pos = g->q_pos;
+    a.K = (const bf16_t*)g->k_cache;
+    a.V = (const bf16_t*)g->v_cache;
+    a.kv_hstride = (long)g->cap * g->head_dim;
+    a.kv_bstride = a.kv_hstride * g->n_kv_heads;
+    a.kv_len = g->kv_len;
+    a.Hkv = g->n_kv_heads;
+    a.D = g->head_dim;
+    a.G = G;
+    a.causal = g->causal;
+    a.window = g->window;
+    a.scale = g->scale;
+    a.softcap = g->softcap;
+    a.eager = g->softcap > 0.f;   // as attn_packed (engine.hip)
+    a.nsplit = 1;
+    a.chunk = g->cap;
+    a.O = (bf16_t*)g->out;
+    a.ldo = a.ldq;
+    RC(attention(a, (hipStream_t)stream));
     return T5G_OK;
 }
 

@@ -35,6 +35,13 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.LayerWeights) == 13 * 8
     assert C.sizeof(_lib.AttnDecodeArgs) == 4 * 4 + 3 * 8 + 8 + 8 + 4 * 4 + 2 * 8
     assert C.sizeof(_lib.GemvArgs) == 152
+    # the three kernel-test hooks (csrc/engine_hooks.hip static_asserts the same sizes)
+    assert C.sizeof(_lib.AttnPackedArgs) == 4 * 4 + 6 * 8 + 6 * 4 + 8
+    assert C.sizeof(_lib.RopeStoreArgs) == 2 * 8 + 10 * 4 + 6 * 8 + 2 * 4 + 2 * 8 + 2 * 8 + 8
+    assert C.sizeof(_lib.NormSrcArgs) == 2 * 4 + 3 * 8 + 2 * 4 + 8 + 2 * 4 + 3 * 8 + 2 * 4 + 6 * 8
+    assert _lib.AttnPackedArgs.out.offset == 88 and _lib.AttnPackedArgs.cap.offset == 64
+    assert _lib.RopeStoreArgs.pos.offset == 56 and _lib.RopeStoreArgs.c_bstride.offset == 128
+    assert _lib.NormSrcArgs.part.offset == 40 and _lib.NormSrcArgs.resid_out.offset == 88
 
 
 def test_packed_bytes():
@@ -107,6 +114,97 @@ def test_attention_decode_reports_unbuilt_geometry(D, G):
                             kv_len=16, causal=1, window=0, scale=D ** -0.5, out=16, work=16)
     assert L.t5g_attention_decode(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
     assert L.t5g_attention_decode_flash(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+
+
+def _packed_args(**kw):
+    """A t5g_attention_packed call that would be valid (pointers are never dereferenced: every
+    case below is rejected before a launch), with fields overridden."""
+    from t5gemma_tts_amd import _lib
+    f = dict(Mq=4, n_heads=8, n_kv_heads=4, head_dim=256, q=16, q_row=16, q_pos=16, k_cache=16, v_cache=16,
+             kv_len=16, cap=256, causal=1, window=0, scale=1 / 16, softcap=0.0, out=16)
+    f.update(kw)
+    return _lib.AttnPackedArgs(**f)
+
+
+def _rope_args(**kw):
+    from t5gemma_tts_amd import _lib
+    f = dict(X=16, Xpart=None, nsplit=0, ldx=4096, M=5, D=256, nq=8, nk=4, nv=4, col0=0, rope_q=1, rope_k=1,
+             pos=16, inv_freq=16, tok_row=16, tok_t=16, kv_len=16, Qout=32, ldq=2048, Kc=16, Vc=16,
+             c_bstride=4 * 64 * 256, c_hstride=64 * 256, rope_tab=None)
+    f.update(kw)
+    return _lib.RopeStoreArgs(**f)
+
+
+def _norm_args(**kw):
+    from t5gemma_tts_amd import _lib
+    f = dict(M=3, d=2304, delta=16, resid=16, post_w=16, pre_w=16, eps=1e-6, resid_out=16, normed_out=16)
+    f.update(kw)
+    return _lib.NormSrcArgs(**f)
+
+
+@pytest.mark.parametrize("kw", [dict(q=None), dict(k_cache=None), dict(v_cache=None), dict(kv_len=None),
+                                dict(out=None), dict(reserved=1), dict(Mq=0), dict(cap=0), dict(cap=-3),
+                                dict(n_kv_heads=0), dict(n_heads=7), dict(head_dim=0), dict(window=-1),
+                                # scores of one query: G * cap * 4 bytes <= 96 KiB
+                                dict(cap=12289), dict(n_heads=4, cap=12289)],
+                         ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+def test_attention_packed_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd import _lib
+    assert _lib.lib().t5g_attention_packed(C.byref(_packed_args(**kw)), None) == _lib.T5G_EINVAL
+
+
+def test_attention_packed_null_struct_and_unbuilt_geometry():
+    """(head_dim, group) = (64, 4) has no attn_kernel: T5G_EUNSUPPORTED, also where its scores
+    would not fit; 12 288 keys at G = 2 (exactly 96 KiB) pass the size check and are refused
+    only for their geometry here."""
+    from t5gemma_tts_amd import _lib
+    L = _lib.lib()
+    assert L.t5g_attention_packed(None, None) == _lib.T5G_EINVAL
+    for D, G in ((64, 4), (128, 1), (96, 2), (256, 4)):
+        for cap in (200, 12289):
+            a = _packed_args(n_heads=2 * G, n_kv_heads=2, head_dim=D, cap=cap)
+            assert L.t5g_attention_packed(C.byref(a), None) == _lib.T5G_EUNSUPPORTED, (D, G, cap)
+
+
+@pytest.mark.parametrize("kw", [dict(X=None), dict(Xpart=16, nsplit=2), dict(reserved=1), dict(M=0), dict(D=0), dict(D=255),
+                                dict(nq=0, nk=0, nv=0), dict(nq=-1), dict(col0=-8), dict(ldx=4095),
+                                dict(col0=8), dict(Qout=None), dict(ldq=2040), dict(Kc=None), dict(Vc=None),
+                                dict(tok_t=None, kv_len=None), dict(c_hstride=255), dict(pos=None),
+                                dict(inv_freq=None),
+                                # split-K slabs: 1 to 8
+                                dict(X=None, Xpart=16, nsplit=9), dict(X=None, Xpart=16, nsplit=0),
+                                # q in place needs one row stride
+                                dict(Qout=16, ldq=2048)],
+                         ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+def test_rope_store_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd import _lib
+    L = _lib.lib()
+    assert L.t5g_rope_store(C.byref(_rope_args(**kw)), None) == _lib.T5G_EINVAL
+    assert L.t5g_rope_store(None, None) == _lib.T5G_EINVAL
+
+
+@pytest.mark.parametrize("kw", [dict(M=0), dict(d=0), dict(d=2300), dict(d=8200), dict(d=8196), dict(delta=None),
+                                dict(ids=16), dict(delta=None, ids=16), dict(delta=None, ids=16, table=16),
+                                dict(delta=None, part=16, nsplit=9, ldp=2304),
+                                dict(delta=None, part=16, nsplit=0, ldp=2304),
+                                dict(delta=None, part=16, nsplit=2, ldp=2296),
+                                dict(delta=None, part=16, nsplit=2, ldp=2306),
+                                dict(resid_out=None, normed_out=None), dict(normed_out=None),
+                                dict(rope_tab=16), dict(rope_tab=16, rope_pos=16, rope_inv_freq=16, rope_D=255),
+                                dict(delta=None, ids=16, table=16, n_table=300, out_rows=16, resid=None)],
+                         ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+def test_resid_norm_src_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd import _lib
+    L = _lib.lib()
+    assert L.t5g_resid_norm_src(C.byref(_norm_args(**kw)), None) == _lib.T5G_EINVAL
+    assert L.t5g_resid_norm_src(None, None) == _lib.T5G_EINVAL
+
+
+def test_resid_norm_src_out_rows_with_slabs_is_unsupported():
+    """The slabs' row stride is the launch's row count, so a row subset of them has no meaning."""
+    from t5gemma_tts_amd import _lib
+    a = _norm_args(delta=None, part=16, nsplit=2, ldp=2304, out_rows=16)
+    assert _lib.lib().t5g_resid_norm_src(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
 
 
 def test_status_codes_map_to_python_errors():
