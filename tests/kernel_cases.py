@@ -4,7 +4,10 @@ and test_gpu_norm_sources.py launch the kernels; tests/test_kernel_cases_cpu.py 
 no GPU, what those tests rely on before they launch anything -- that a window one key longer or
 shorter moves every marked query of the chosen seeds by ten times the bound, that a lost block
 rescale moves the windowed block cases as far, that the slab values tell a slab order, and that
-the share of RoPE pairs next to a bf16 tie is what the safe-set rule expects.
+the share of RoPE pairs next to a bf16 tie is what the safe-set rule expects. Also the decode
+attention call and its fp64 reference (tests/test_gpu_attention.py, test_gpu_attn_chunk_scores.py)
+and the order-revealing bf16 generator of the exact-order tests; tests/test_engine_cases_cpu.py
+pins what they draw.
 """
 import functools
 
@@ -20,6 +23,25 @@ def i16(t):
 
 def sentinel(*shape):
     return torch.full(shape, SENT, dtype=torch.int16).view(BF16)
+
+
+def hdr_bf16(shape, g):
+    """bf16 values over a wide exponent range plus rare huge entries: sums whose bits
+    depend on the association order (a plain randn rarely exposes a wrong order)."""
+    v = torch.randn(shape, generator=g) * torch.exp2(torch.randint(-10, 11, shape, generator=g).float())
+    big = torch.rand(shape, generator=g) < 4.0 / shape[-1]
+    return torch.where(big, torch.randn(shape, generator=g) * 2.0 ** 14, v).to(BF16)
+
+
+EPS = 1e-6
+
+
+def rms_norm(x, w):
+    """The model's RMSNorm in fp32, (1 + w) scaling, rounded to bf16 once (tests/test_gpu_gemv.py,
+    test_gpu_norm_sources.py)."""
+    xf = x.float()
+    r = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + EPS)
+    return ((xf * r) * (1.0 + w.float())).to(BF16)
 
 
 # ---------------------------------------------------------------------------
@@ -111,6 +133,63 @@ def exact_attention(q, K, V, lens, rows, pos, scale, causal, window=0, softcap=0
 def attn_bound(exact):
     """The project's bound for the aten-order form (tests/test_gpu_attention.py)."""
     return 2.0 ** -6 * max(1.0, exact.abs().max().item())
+
+
+# ---------------------------------------------------------------------------
+# decode attention (one query per row, at the row's last key): tests/test_gpu_attention.py and
+# tests/test_gpu_attn_chunk_scores.py
+def decode_exact_attention(q, K, V, lens, scale, window=0):
+    """fp64 softmax attention of each row's query (at position lens[b] - 1) over its keys
+    [lo, lens[b]), lo = max(0, lens[b] - window) for a sliding window, else 0."""
+    B, Hq, D = q.shape
+    G = Hq // K.shape[1]
+    out = torch.zeros(B, Hq, D, dtype=torch.float64)
+    for b in range(B):
+        L = int(lens[b])
+        lo = max(0, L - window) if window > 0 else 0
+        for h in range(Hq):
+            s = (K[b, h // G, lo:L].double() @ q[b, h].double()) * scale
+            out[b, h] = torch.softmax(s, 0) @ V[b, h // G, lo:L].double()
+    return out
+
+
+def decode_attention_call(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flash=False, window=0, cap=None,
+                          prepare=None, want_rc=0):
+    """One t5g_attention_decode(_flash) call on random bf16 q / K / V (attn_inputs, one query
+    per row); returns the output (fp64, [B][Hq][D]) and the host inputs. cap: cache slots per
+    (row, kv head), default L; prepare(q, K, V) edits the inputs in place before the upload;
+    want_rc != 0: the call must return that status and write nothing (returns None)."""
+    import ctypes as C
+    from t5gemma_tts_amd import _lib
+    lib = _lib.lib()
+    cap = L if cap is None else cap
+    q, K, V = attn_inputs(seed, B, Hq, Hkv, D, B, cap)
+    if prepare is not None:
+        prepare(q, K, V)
+    dev = "cuda"
+    qd, Kd, Vd = q.to(dev), K.to(dev), V.to(dev)
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+    out = torch.zeros(B, Hq * D, dtype=BF16, device=dev)
+    nb = lib.t5g_attention_decode_work_bytes(B, Hq, Hkv, D, cap)
+    assert nb > 0
+    work = torch.zeros(nb // 4, dtype=torch.float32, device=dev)   # flash: tickets start at zero
+    a = _lib.AttnDecodeArgs(B=B, n_heads=Hq, n_kv_heads=Hkv, head_dim=D, q=qd.data_ptr(), k_cache=Kd.data_ptr(),
+                            v_cache=Vd.data_ptr(), cap=cap, kv_len=lens_d.data_ptr(), causal=causal, window=window,
+                            scale=D ** -0.5, out=out.data_ptr(), work=work.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    fn = lib.t5g_attention_decode_flash if flash else lib.t5g_attention_decode
+    if want_rc != 0:
+        assert fn(C.byref(a), st) == want_rc
+        torch.cuda.synchronize()
+        assert int((out != 0).sum().item()) == 0 and int((work != 0).sum().item()) == 0   # nothing launched
+        return None
+    _lib.check(fn(C.byref(a), st), "attention_decode")
+    torch.cuda.synchronize()
+    got = out.cpu().view(B, Hq, D).double()
+    if flash:   # the tickets are left at zero for the next call
+        nt = B * Hkv
+        assert int(work[-nt:].view(torch.int32).abs().sum().item()) == 0
+    return got, q, K, V
 
 
 # window edges. A marked query is (row, t, marker key, alt): the marker -- 8 q / |q| for head 0

@@ -12,51 +12,18 @@ writes, captured from the reference in tests/golden/make_golden_export.py -- rea
 * the directory's tensors are the ones the reference model held (sha256 pinned);
 * sharded safetensors with an index load like a single file."""
 import json
-import os
 import tempfile
 
 import pytest
-import torch
 
-from conftest import GOLDEN
+from conftest import GOLDEN  # noqa: F401  (sys.path set-up)
 
 import t5gemma_tts_amd  # noqa: F401
 from t5gemma_tts_amd.config import VoiceConfig, named_config
 from t5gemma_tts_amd.weights import (check_state_dict, load_hf_checkpoint, state_dict_digest, synthetic_weights,
                                      weight_shapes)
-
-
-def _fixture():
-    with open(os.path.join(GOLDEN, "golden_export.json")) as f:
-        return json.load(f)
-
-
-def write_export(path, fx=None, config_overrides=None, unpruned=False, shards=2):
-    """An export directory of the golden_tiny_eager model: config.json + safetensors shards
-    (+ model.safetensors.index.json), tensors under the reference export's names."""
-    from safetensors.torch import save_file
-    fx = fx or _fixture()
-    cfg = named_config(fx["config"], **fx["config_kw"])
-    sd = synthetic_weights(cfg, fx["weight_seed"])
-    tensors = {k: sd[k] for k in fx["state_dict"]}
-    if unpruned:
-        for k, shape in fx["state_dict_unpruned_extra"].items():
-            tensors[k] = torch.zeros(shape, dtype=torch.bfloat16)
-    conf = dict(fx["config_json"])
-    conf.update(config_overrides or {})
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(conf, f, indent=2)
-    names = sorted(tensors)
-    weight_map = {}
-    for i in range(shards):
-        part = names[i::shards]
-        fn = f"model-{i + 1:05d}-of-{shards:05d}.safetensors"
-        save_file({k: tensors[k].contiguous() for k in part}, os.path.join(path, fn), metadata={"format": "pt"})
-        weight_map.update({k: fn for k in part})
-    with open(os.path.join(path, "model.safetensors.index.json"), "w") as f:
-        json.dump({"metadata": {}, "weight_map": weight_map}, f)
-    return cfg, sd
+from tests.fixture_cases import export_fixture as _fixture
+from tests.fixture_cases import write_export
 
 
 def test_export_tensor_names_are_the_engine_weight_table():

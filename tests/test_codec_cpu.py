@@ -5,13 +5,13 @@ import ctypes as C
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN
+from tests.engine_cases import header_symbols
 
 CASES = ["tiny", "full16k", "hop882"]
 
@@ -77,17 +77,11 @@ def test_irfft_basis_matches_torch():
     assert torch.allclose(got, ref, atol=1e-6, rtol=0), (got - ref).abs().max()
 
 
-def _header_symbols():
-    src = open(os.path.join(REPO, "include", "xc2.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(xc2_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_xc2_exports_and_struct_sizes():
     from t5gemma_tts_amd import _lib
     from t5gemma_tts_amd import codec
     L = _lib.lib()
-    syms = _header_symbols()
+    syms = header_symbols("xc2.h", "xc2")
     assert set(syms) == set(codec.XC2_SIGNATURES), set(syms) ^ set(codec.XC2_SIGNATURES)
     for s in syms:
         assert hasattr(L, s), s

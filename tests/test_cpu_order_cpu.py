@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, REPO
+from tests.kernel_cases import hdr_bf16
 
 BF16 = torch.bfloat16
 
@@ -28,12 +29,6 @@ def _reference_host():
 
 
 ref_host = pytest.mark.skipif(not _reference_host(), reason="torch comparison needs the reference host (AMX, torch 2.10)")
-
-
-def _hdr(shape, g):
-    v = torch.randn(shape, generator=g) * torch.exp2(torch.randint(-10, 11, shape, generator=g).float())
-    big = torch.rand(shape, generator=g) < 4.0 / shape[-1]
-    return torch.where(big, torch.randn(shape, generator=g) * 2.0 ** 14, v).to(BF16)
 
 
 @ref_host
@@ -57,10 +52,10 @@ def test_linear_order_matches_torch(M, N, K):
     from oracle import cpu_order
     torch.set_num_threads(8)
     g = torch.Generator().manual_seed(M + N + K)
-    x = _hdr((M, K), g)
+    x = hdr_bf16((M, K), g)
     cols = torch.randperm(N, generator=g)[:64]
     w = torch.zeros(N, K, dtype=BF16)
-    w[cols] = _hdr((64, K), g)
+    w[cols] = hdr_bf16((64, K), g)
     ref = F.linear(x, w)[:, cols]
     kb = cpu_order.ksplit(N, K, M)
     got = torch.from_numpy(cpu_order.linear_f32(x.float().numpy(), w[cols].float().numpy(), kb)).to(BF16)

@@ -7,22 +7,9 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.fixture_cases import planted_matrix
+
 BF16 = torch.bfloat16
-
-
-def planted_matrix(N, K, seed):
-    """Random normal x 0.02 with the rows the rule's edges sit on: an all-zero row, amax =
-    448 * 2^-3 (e = -3 exactly), amax = 464 * 2^-3 (just past it: e = -2), and 3.0 next to
-    1e-4-scale values (most of the row lands in e4m3's subnormals)."""
-    g = torch.Generator().manual_seed(seed)
-    W = (torch.randn(N, K, generator=g) * 0.02).to(BF16)
-    W[3] = 0
-    W[5] = (W[5].float().clamp(-1, 1)).to(BF16)
-    W[5, 7] = 448 * 2.0 ** -3
-    W[6, K - 1] = -464 * 2.0 ** -3
-    W[9] = (torch.randn(K, generator=g) * 1e-4).to(BF16)
-    W[9, 0] = 3.0
-    return W
 
 
 @pytest.mark.parametrize("N,K", [(40, 96), (208, 2304)])

@@ -19,11 +19,11 @@ import pytest
 import torch
 
 from tests import kernel_cases as kc
+from tests.engine_cases import need_gpu
 from tests.kernel_cases import BF16
 from tests.kernel_cases import attn_bound as _bound
 from tests.kernel_cases import attn_inputs as _inputs
 from tests.kernel_cases import exact_attention as _exact
-from tests.test_gpu_attention import _need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -92,7 +92,7 @@ def _prefill_case():
 def test_prefill_every_position():
     """8 q / 4 kv heads x 256, rows of 1, 70 and 200 keys in a cache of 256 slots, causal: all
     271 positions in one launch. The unused slots hold K = 1e4 and V = NaN."""
-    _need_gpu()
+    need_gpu()
     q, K, V, rows, pos = _prefill_case()
     got = _run(q, K, V, PREFILL_LENS, rows, pos, causal=1)
     exact = _exact(q, K, V, PREFILL_LENS, rows, pos, 256 ** -0.5, True)
@@ -107,7 +107,7 @@ def test_prefill_every_position():
 def test_batch_invariance():
     """A query launched alone is bitwise the same query inside the packed batch (one workgroup
     per (query, kv head), nothing shared between queries)."""
-    _need_gpu()
+    need_gpu()
     q, K, V, rows, pos = _prefill_case()
     got = _run(q, K, V, PREFILL_LENS, rows, pos, causal=1)
     for i in (0, 1 + 69, 1 + 70 + 131):
@@ -124,7 +124,7 @@ def test_window_edges(causal, W):
     queries in mid row, at t = W - 1 and at t = W. Bidirectional (the encoder's |t - k| <= W):
     keys at t - W - 1 / t - W and t + W + 1 / t + W, for queries in mid row, with t < W, with
     t + W >= len, and in rows shorter than the window. Ragged rows in a larger cache."""
-    _need_gpu()
+    need_gpu()
     q, K, V, lens, rows, pos, exact, bound, move = kc.window_case(causal, W)
     got = _run(q, K, V, lens, rows, pos, causal, W)
     err = (got.double() - exact).abs().amax(dim=(1, 2))
@@ -138,7 +138,7 @@ def test_window_edges(causal, W):
 def test_cross_attention_ignores_query_positions():
     """Prefill cross attention: non-causal, no window, text rows of 60, 1 and 33 keys; the query
     positions are audio positions (up to 200, past every kv_len) and must not matter."""
-    _need_gpu()
+    need_gpu()
     lens = [60, 1, 33]
     rows = [0] * 7 + [1] * 4 + [2] * 6
     pos = [0, 59, 60, 61, 150, 200, 7, 0, 1, 90, 200, 0, 32, 33, 34, 120, 200]
@@ -163,7 +163,7 @@ def test_several_aten_blocks():
     """One row of 1 100 keys, keys with scores about +8 and +9 planted in the second and third
     512-key block (kernel_cases.blocks_case): causal queries on both sides of the block edges
     and of the planted keys."""
-    _need_gpu()
+    need_gpu()
     q, K, V = kc.blocks_case()
     T = kc.BLOCK_T
     lens, rows, scale = [kc.BLOCK_LEN], [0] * len(T), 256 ** -0.5
@@ -186,7 +186,7 @@ def test_blocks_counted_from_lo(window):
     but j0 / 512 = 2 -- an index that forgets lo reads another slot. The planted keys fall in
     the first and second block either way, so the rescale matters: losing it moves the
     reference by ten times the bound (asserted in kernel_cases.blocks_window_case)."""
-    _need_gpu()
+    need_gpu()
     q, K, V = kc.blocks_case()
     qi, exact, bound, shift = kc.blocks_window_case(window)
     got = _run(qi, K, V, [kc.BLOCK_LEN], [0], [kc.BLOCK_LEN - 1], causal=1, window=window)
@@ -201,7 +201,7 @@ def test_blocks_counted_from_lo(window):
 def test_all_instantiated_geometries(D, G):
     """Every (head_dim, group) attention() instantiates, with 2 and 4 kv heads, causal and
     bidirectional, window 0 and 50; ragged rows up to 200 keys, 14 queries."""
-    _need_gpu()
+    need_gpu()
     lens = [200, 1, 65, 137]
     rows = [0, 0, 0, 0, 0, 1, 2, 2, 2, 2, 3, 3, 3, 3]
     pos = [0, 49, 50, 120, 199, 0, 0, 13, 51, 64, 0, 68, 100, 136]
@@ -220,7 +220,7 @@ def test_all_instantiated_geometries(D, G):
 def test_rows_past_8192_keys():
     """8 200 score slots at G = 2 are 65 600 bytes of LDS: the launch that opts in to 96 KiB.
     One row, one kv head; t = 8 199 reads every slot. The same query under a window of 5 000."""
-    _need_gpu()
+    need_gpu()
     cap = 8200
     q, K, V = _inputs(8200, 3, 2, 1, 256, 1, cap)
     lens, rows, pos, scale = [cap], [0, 0, 0], [0, 4100, cap - 1], 256 ** -0.5
@@ -243,7 +243,7 @@ def test_eager_softcap(D):
     eager_attention_forward in torch bf16 ops (oracle/t5g_oracle.attention, impl="eager") has
     its own error against fp64 on the same inputs; the kernel's different sum order draws
     independent roundings of the same size, so its error may be up to twice that."""
-    _need_gpu()
+    need_gpu()
     from oracle import t5g_oracle
     L, Hq, Hkv = 100, 4, 2
     q, K, V = _inputs(50 + D, L, Hq, Hkv, D, 1, L)

@@ -11,7 +11,10 @@ The query of a row of `len` keys sits at len - 1, so its window holds keys
 import pytest
 import torch
 
-from tests.test_gpu_attention import BF16, _exact, _need_gpu, _run
+from tests.engine_cases import need_gpu
+from tests.kernel_cases import BF16
+from tests.kernel_cases import decode_attention_call as _run
+from tests.kernel_cases import decode_exact_attention as _exact
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +49,7 @@ def test_window_boundary_is_exact(flash):
     """8 rows x 8 q heads / 4 kv heads x 256; window 100 with row lengths around 100 and
     100 + 64 (the chunk edge of the windowed span), window 64 with lengths 64 / 65 / 128 / 129.
     An off-by-one in `lo` takes a marker key in or out, which moves the output by ~4."""
-    _need_gpu()
+    need_gpu()
     scale = 256 ** -0.5
     for window, lens in ((100, [1, 64, 99, 100, 101, 164, 165, 400]), (64, [64, 65, 128, 129, 129, 128, 65, 64])):
         for flip in (0, 1):
@@ -75,7 +78,7 @@ def test_cap_larger_than_rows(flash):
     """The cache holds more slots than any row uses (cap 1024 over rows of <= 200 keys; cap 129,
     no multiple of the 64-key chunk, over rows of <= 129): the unused slots hold K = 1e4 and
     V = NaN, so a stride or bound slip shows as a huge or NaN output. window 0 and 100."""
-    _need_gpu()
+    need_gpu()
     scale = 256 ** -0.5
     for cap, lens in ((1024, [200, 1, 64, 65, 129, 199, 100, 137]), (129, [129, 128, 65, 64, 1, 100, 129, 77])):
         def prepare(q, K, V, lens=lens):
@@ -96,7 +99,7 @@ def test_cap_larger_than_rows(flash):
 def test_all_instantiated_geometries(D, G):
     """Every (head_dim, group) attention_decode instantiates, with 2 and 4 kv heads, 4 ragged
     rows up to 200 keys, both forms, window 0 and 50."""
-    _need_gpu()
+    need_gpu()
     lens = [200, 1, 65, 137]
     for Hkv in (2, 4):
         for flash in (False, True):
@@ -112,6 +115,6 @@ def test_all_instantiated_geometries(D, G):
 @pytest.mark.parametrize("flash", [False, True], ids=["aten_order", "flash"])
 def test_uninstantiated_geometry_is_unsupported(flash):
     """(head_dim, group) = (64, 4) is not built: T5G_EUNSUPPORTED, and nothing is launched."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     assert _run(200, 4, [200, 1, 65, 137], Hq=8, Hkv=2, D=64, flash=flash, want_rc=_lib.T5G_EUNSUPPORTED) is None

@@ -9,67 +9,16 @@ path -> flash chunks) mid-call, the three placements of the attention bitwise eq
 (tests/test_gpu_attention.py's flash bounds): max |err| <= 2^-7 max(1, max |exact|), mean
 error <= 1.5 x the aten-order form's; rows of <= 64 keys equal the aten-order form bit for
 bit. Reference: [tf] modeling_t5gemma.py:264-304."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN  # noqa: F401  (sys.path set-up)
+from tests.engine_cases import assert_same_run, both_loops, mid_config, need_gpu
+from tests.kernel_cases import decode_attention_call as _run
+from tests.kernel_cases import decode_exact_attention as _exact
 
 pytestmark = pytest.mark.gpu
-BF16 = torch.bfloat16
 SCALE = 256 ** -0.5
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs the MI355X")
-
-
-def _exact(q, K, V, lens, scale, window=0):
-    """fp64 softmax attention of each row's query (at position lens[b] - 1) over its keys
-    [lo, lens[b]), lo = max(0, lens[b] - window) for a sliding window, else 0."""
-    B, Hq, D = q.shape
-    G = Hq // K.shape[1]
-    out = torch.zeros(B, Hq, D, dtype=torch.float64)
-    for b in range(B):
-        L = int(lens[b])
-        lo = max(0, L - window) if window > 0 else 0
-        for h in range(Hq):
-            s = (K[b, h // G, lo:L].double() @ q[b, h].double()) * scale
-            out[b, h] = torch.softmax(s, 0) @ V[b, h // G, lo:L].double()
-    return out
-
-
-def _run(L, B, lens, Hq=8, Hkv=4, D=256, seed=0, flash=False, window=0, cap=None, prepare=None):
-    """One t5g_attention_decode(_flash) call on random bf16 q / K / V (causal); returns the
-    output (fp64, [B][Hq][D]) and the host inputs. cap: cache slots per (row, kv head),
-    default L; prepare(q, K, V) edits the inputs in place before the upload."""
-    from t5gemma_tts_amd import _lib
-    lib = _lib.lib()
-    g = torch.Generator().manual_seed(seed)
-    cap = L if cap is None else cap
-    q = torch.randn(B, Hq, D, generator=g).to(BF16)
-    K = torch.randn(B, Hkv, cap, D, generator=g).to(BF16)
-    V = torch.randn(B, Hkv, cap, D, generator=g).to(BF16)
-    if prepare is not None:
-        prepare(q, K, V)
-    dev = "cuda"
-    qd, Kd, Vd = q.to(dev), K.to(dev), V.to(dev)
-    lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
-    out = torch.zeros(B, Hq * D, dtype=BF16, device=dev)
-    nb = lib.t5g_attention_decode_work_bytes(B, Hq, Hkv, D, cap)
-    assert nb > 0
-    work = torch.zeros(nb // 4, dtype=torch.float32, device=dev)   # flash: tickets start at zero
-    a = _lib.AttnDecodeArgs(B=B, n_heads=Hq, n_kv_heads=Hkv, head_dim=D, q=qd.data_ptr(), k_cache=Kd.data_ptr(),
-                            v_cache=Vd.data_ptr(), cap=cap, kv_len=lens_d.data_ptr(), causal=1, window=window,
-                            scale=SCALE, out=out.data_ptr(), work=work.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fn = lib.t5g_attention_decode_flash if flash else lib.t5g_attention_decode
-    _lib.check(fn(C.byref(a), st), "attention_decode")
-    torch.cuda.synchronize()
-    return out.cpu().view(B, Hq, D).double(), q, K, V
 
 
 def _check(tag, L, lens, seed, window=0, cap=None, prepare=None):
@@ -94,21 +43,21 @@ def _check(tag, L, lens, seed, window=0, cap=None, prepare=None):
 def test_chunk_edges(L):
     """Rows of 1, 64 (one chunk, aten-order path), 65 (a second chunk of one key) and L keys
     (L = 128: two full chunks, 191: a last chunk of 63) in one launch."""
-    _need_gpu()
+    need_gpu()
     _check(f"edges L={L}", L, [L, 65, 64, 1], seed=L)
 
 
 def test_unaligned_chunk_start():
     """A 100-key sliding window: the chunks start at t - 99, so a row's chunks begin at an
     arbitrary key (and its second chunk holds 36 keys)."""
-    _need_gpu()
+    need_gpu()
     _check("window 100", 300, [300, 251, 101, 64], seed=300, window=100)
 
 
 def test_masked_keys_never_leak():
     """70 cache slots past the longest row, every slot past a row's length NaN in K and V:
     no key past the row's last one reaches a score or an output."""
-    _need_gpu()
+    need_gpu()
     L, lens = 191, [191, 130, 65, 64]
 
     def prepare(q, K, V):
@@ -121,7 +70,7 @@ def test_masked_keys_never_leak():
 
 def test_peaked_softmax():
     """q and K scaled by 8 (scores 64 times as large: one key takes nearly all the weight)."""
-    _need_gpu()
+    need_gpu()
 
     def prepare(q, K, V):
         q.mul_(8.0)
@@ -135,15 +84,10 @@ def test_single_to_multi_transition_in_engine():
     generated tokens: the rows cross 64 keys mid-call. The separate flash launch (mode 0) and
     stage S in front (1) and at the end (2) give the same tokens and bitwise the same logits,
     and a second run of mode 2 repeats the first."""
-    _need_gpu()
-    import json
-    import os
-    from t5gemma_tts_amd.config import named_config
-    from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance
-    from t5gemma_tts_amd.weights import synthetic_weights
-    meta = json.load(open(os.path.join(GOLDEN, "golden_mid.json")))
-    cfg = named_config(meta["config"], **meta["config_kw"])
-    sd = synthetic_weights(cfg, meta["weight_seed"])
+    need_gpu()
+    from t5gemma_tts_amd.engine import T5GemmaTTSEngine, Utterance
+    cfg, sd = mid_config()
+    # not engine_cases.mid_engine: max_gen 14
     eng = T5GemmaTTSEngine(cfg, sd, device="cuda:0", max_batch=8, max_text=64, max_audio=128, max_gen=14)
     rng = np.random.default_rng(5866)
     B = 8
@@ -153,24 +97,16 @@ def test_single_to_multi_transition_in_engine():
         x = rng.integers(3, 4000, size=int(rng.integers(4, 40))).tolist()
         utts.append(Utterance(x=x, y=rng.integers(0, 65536, size=tp).tolist() + [cfg.y_sep_token],
                               tgt_y_len=tp + 1 + 12))
-    p = SamplingParams(top_k=30, top_p=0.9, temperature=0.8)
     seeds = list(range(700, 700 + B))
 
     def run(mode):
         eng.set_attn_in_block(mode)   # 0 the separate flash launch, 1 stage S in front, 2 at the end
         before = eng.attn_in_block_launches()
-        out = eng.generate(utts, p, seeds=seeds, parity=True, exact=False, record_logits=True)
-        fast = eng.generate(utts, p, seeds=seeds)
+        out, fast = both_loops(eng, utts, seeds)
         return out, fast, eng.attn_in_block_launches() - before
 
     def same(a, b, tag):
-        for r in range(B):
-            assert a["gen"][r].tolist() == b["gen"][r].tolist(), (tag, r)
-        if "logits" not in a:   # the graph-replayed loop: tokens only
-            return
-        assert len(a["logits"]) == len(b["logits"]), tag
-        for s, (la, lb) in enumerate(zip(a["logits"], b["logits"])):
-            assert torch.equal(la.view(torch.int16), lb.view(torch.int16)), (tag, s)
+        assert_same_run(a, b, B, tag)
 
     o2, f2, n2 = run(2)
     o0, f0, n0 = run(0)

@@ -1,5 +1,5 @@
 """The drop-in loaded from an export-shaped directory (config.json + sharded safetensors
-under the reference export's names, tests/test_checkpoint_cpu.write_export) reproduces the
+under the reference export's names, tests/fixture_cases.write_export) reproduces the
 reference's tokens: ``T5GemmaVoiceForConditionalGeneration.from_pretrained(dir)`` then, per
 golden case, ``torch.manual_seed(seed); inference_tts(...)`` exactly as the reference
 generated the golden (tests/golden/make_golden.py run_case).
@@ -19,13 +19,13 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from tests.fixture_cases import write_export
 
 pytestmark = pytest.mark.gpu
 
 
 def _load(td, **overrides):
     from t5gemma_tts_amd.engine import T5GemmaVoiceForConditionalGeneration
-    from test_checkpoint_cpu import write_export
     write_export(td, shards=2, unpruned=True, config_overrides=overrides or None)
     return T5GemmaVoiceForConditionalGeneration.from_pretrained(td, device="cuda:0", max_batch=1, max_text=64,
                                                                 max_audio=256, max_gen=200)

@@ -19,18 +19,10 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from tests.engine_cases import need_gpu, ptr, stream
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.mark.parametrize("Tq,Tk,causal,qscale", [
@@ -40,7 +32,7 @@ def _st():
     (152, 60, 0, 4.0),
 ])
 def test_eager_attention_bitwise_vs_oracle(Tq, Tk, causal, qscale):
-    _need_gpu()
+    need_gpu()
     from oracle import cpu_order
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -62,10 +54,10 @@ def test_eager_attention_bitwise_vs_oracle(Tq, Tk, causal, qscale):
         q_row = torch.zeros(Tq, **i32)
         q_pos = torch.arange(Tq, **i32)
         q_len = torch.tensor([Tq], **i32)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = L.t5g_eager_attention(C.c_void_p(qd.data_ptr()), Tq, p(q_row), p(q_pos), p(q_len), C.c_void_p(kd.data_ptr()),
-                               C.c_void_p(vd.data_ptr()), cap, C.c_void_p(kv_len.data_ptr()), Hq, Hkv, D, causal, 0,
-                               1.0 / 16, 50.0, C.c_void_p(lut.data_ptr()), C.c_void_p(o.data_ptr()), _st())
+    rc = L.t5g_eager_attention(C.c_void_p(qd.data_ptr()), Tq, ptr(q_row), ptr(q_pos), ptr(q_len),
+                               C.c_void_p(kd.data_ptr()), C.c_void_p(vd.data_ptr()), cap,
+                               C.c_void_p(kv_len.data_ptr()), Hq, Hkv, D, causal, 0, 1.0 / 16, 50.0,
+                               C.c_void_p(lut.data_ptr()), C.c_void_p(o.data_ptr()), stream())
     assert rc == 0
     torch.cuda.synchronize()
     got = o.cpu().view(Tq, Hq, D).transpose(0, 1)

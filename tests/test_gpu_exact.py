@@ -15,39 +15,18 @@ import torch
 
 from conftest import GOLDEN, REPO
 
+from tests.engine_cases import golden_params, load_golden, need_gpu, stream
+from tests.kernel_cases import hdr_bf16
+
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name + ".json")) as f:
-        meta = json.load(f)
-    npz = os.path.join(GOLDEN, name + ".npz")
-    return meta, (dict(np.load(npz)) if os.path.exists(npz) else {})
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _pack(L, W):
     N, K = W.shape
     Wp = torch.empty(L.t5g_packed_bytes(N, K) // 2, dtype=BF16, device="cuda")
-    assert L.t5g_pack_weight(C.c_void_p(W.data_ptr()), N, K, K, C.c_void_p(Wp.data_ptr()), _st()) == 0
+    assert L.t5g_pack_weight(C.c_void_p(W.data_ptr()), N, K, K, C.c_void_p(Wp.data_ptr()), stream()) == 0
     return Wp
-
-
-def _hdr(shape, g):
-    """bf16 values over a wide exponent range plus rare huge entries: sums whose bits
-    depend on the association order (a plain randn rarely exposes a wrong order)."""
-    v = torch.randn(shape, generator=g) * torch.exp2(torch.randint(-10, 11, shape, generator=g).float())
-    big = torch.rand(shape, generator=g) < 4.0 / shape[-1]
-    return torch.where(big, torch.randn(shape, generator=g) * 2.0 ** 14, v).to(BF16)
 
 
 # ------------------------------------------------------------------------- Linear
@@ -66,13 +45,13 @@ def _hdr(shape, g):
 def test_exact_linear_bitwise_vs_cpu_order(M, N, K, kb, epi, fn):
     """t5g_exact_linear (VALU chains) and t5g_xmm_linear (the engine's f32-MFMA chains) ==
     oracle.cpu_order.linear (the reference host's F.linear order)."""
-    _need_gpu()
+    need_gpu()
     from oracle import cpu_order
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     g = torch.Generator().manual_seed(M * 131 + N + kb)
-    X = _hdr((M, K), g)
-    W = _hdr((N, K), g)
+    X = hdr_bf16((M, K), g)
+    W = hdr_bf16((N, K), g)
     bias = (torch.randn(N, generator=g)).to(BF16)
     Wp = _pack(L, W.cuda())
     Xd, bd = X.cuda(), bias.cuda()
@@ -81,7 +60,7 @@ def test_exact_linear_bitwise_vs_cpu_order(M, N, K, kb, epi, fn):
     Y = torch.zeros(M, n_out, dtype=torch.float32 if epi == 4 else BF16, device="cuda")
     rc = getattr(L, fn)(C.c_void_p(Xd.data_ptr()), K, M, C.c_void_p(Wp.data_ptr()), N, K, kb // 32,
                             C.c_void_p(bd.data_ptr()), C.c_void_p(lut.data_ptr()), C.c_void_p(Y.data_ptr()), n_out,
-                            epi, _st())
+                            epi, stream())
     assert rc == 0
     torch.cuda.synchronize()
     y32 = cpu_order.linear_f32(X.float().numpy(), W.float().numpy(), kb or None)
@@ -111,19 +90,19 @@ def test_xmm_decode_parts_bitwise(M, N, K, kb):
     """The decode part mode (one workgroup per (group, K part), the engine's down projection
     at M = 1): each part's fp32 fold, added in order from 0 as the consumer norm does, ==
     the reference order's unrounded sum (oracle.cpu_order.linear_f32 with the same split)."""
-    _need_gpu()
+    need_gpu()
     from oracle import cpu_order
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     g = torch.Generator().manual_seed(M * 71 + N + kb)
-    X = _hdr((M, K), g)
-    W = _hdr((N, K), g)
+    X = hdr_bf16((M, K), g)
+    W = hdr_bf16((N, K), g)
     Wp = _pack(L, W.cuda())
     Xd = X.cuda()
     parts = -(-K // kb)
     Y = torch.full((parts, M, N), float("nan"), dtype=torch.float32, device="cuda")
     rc = L.t5g_xmm_linear(C.c_void_p(Xd.data_ptr()), K, M, C.c_void_p(Wp.data_ptr()), N, K, kb // 32, None, None,
-                          C.c_void_p(Y.data_ptr()), N, 0x2000 | 4, _st())
+                          C.c_void_p(Y.data_ptr()), N, 0x2000 | 4, stream())
     assert rc == 0
     torch.cuda.synchronize()
     p = Y.cpu().numpy()
@@ -142,7 +121,7 @@ def test_decode_attention_launches_bitwise_vs_cpu_order(Tk, window, G):
     """The engine's decode attention launches (csrc/xattn.hip: the scores launch, four threads
     per key keeping the gemv's lane accumulators, and the P.V launch) == oracle.cpu_order.sdpa
     for one query per row at its last key: 3 rows of different lengths, 4 kv heads."""
-    _need_gpu()
+    need_gpu()
     from oracle import cpu_order
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -163,7 +142,7 @@ def test_decode_attention_launches_bitwise_vs_cpu_order(Tk, window, G):
     qd, kd, vd = q.reshape(B, Hq * D).cuda(), kc.cuda(), vc.cuda()   # held: the call reads them
     rc = L.t5g_exact_attention(C.c_void_p(qd.data_ptr()), B, None, None, None, C.c_void_p(kd.data_ptr()),
                                C.c_void_p(vd.data_ptr()), cap, C.c_void_p(kv_len.data_ptr()), Hq, Hkv, D, 1,
-                               window, 1.0 / 16, 8, C.c_void_p(o.data_ptr()), _st())
+                               window, 1.0 / 16, 8, C.c_void_p(o.data_ptr()), stream())
     assert rc == 0
     torch.cuda.synchronize()
     got = o.cpu().view(B, Hq, D)
@@ -184,7 +163,7 @@ def test_decode_attention_launches_bitwise_vs_cpu_order(Tk, window, G):
 def test_exact_attention_bitwise_vs_cpu_order(Tq, Tk, causal, window):
     """t5g_exact_attention == oracle.cpu_order.sdpa (aten CPU flash attention + the GEMM it
     selects) for decode, prefill, cross and encoder shapes, 8 q heads over 4 kv heads."""
-    _need_gpu()
+    need_gpu()
     from oracle import cpu_order
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -206,7 +185,7 @@ def test_exact_attention_bitwise_vs_cpu_order(Tq, Tk, causal, window):
     rc = L.t5g_exact_attention(C.c_void_p(qd.data_ptr()), Tq, C.c_void_p(q_row.data_ptr()),
                                C.c_void_p(q_pos.data_ptr()), C.c_void_p(q_len.data_ptr()), C.c_void_p(kd.data_ptr()),
                                C.c_void_p(vd.data_ptr()), cap, C.c_void_p(kv_len.data_ptr()), Hq, Hkv, D, causal,
-                               window, 1.0 / 16, 8, C.c_void_p(out.data_ptr()), _st())
+                               window, 1.0 / 16, 8, C.c_void_p(out.data_ptr()), stream())
     assert rc == 0
     torch.cuda.synchronize()
     # the reference call: decode sliding-window layers see the last `window` keys (all
@@ -234,12 +213,6 @@ def _engine(cfg, sd, **kw):
     return T5GemmaTTSEngine(cfg, sd, device="cuda:0", **kw)
 
 
-def _params(c):
-    from t5gemma_tts_amd.engine import SamplingParams
-    return SamplingParams(top_k=c["top_k"], top_p=c["top_p"], min_p=c["min_p"], temperature=c["temperature"],
-                          stop_repetition=c["stop_repetition"], silence_tokens=tuple(c["silence_tokens"]))
-
-
 def _sha(row_bits):
     return hashlib.sha256(row_bits.astype(np.int16).tobytes()).hexdigest()[:16]
 
@@ -250,7 +223,7 @@ def _run_golden(name, max_audio=256, max_text=64, max_gen=200, cases=None, batch
     from t5gemma_tts_amd.weights import synthetic_weights
     if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
         pytest.skip("fixture missing")
-    meta, arrs = _load(name)
+    meta, arrs = load_golden(name)
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     eng = _engine(cfg, sd, max_batch=max(batch, 1), max_text=max_text, max_audio=max_audio, max_gen=max_gen)
@@ -260,7 +233,7 @@ def _run_golden(name, max_audio=256, max_text=64, max_gen=200, cases=None, batch
         idx = todo[i0:i0 + batch]
         cs = [meta["cases"][i] for i in idx]
         utts = [Utterance(x=c["x"], y=c["y"], tgt_y_len=c["tgt"]) for c in cs]
-        out = eng.generate(utts, [_params(c) for c in cs], seeds=[c["seed"] for c in cs], parity=True,
+        out = eng.generate(utts, [golden_params(c) for c in cs], seeds=[c["seed"] for c in cs], parity=True,
                            record_logits=True)
         for b, (ci, c) in enumerate(zip(idx, cs)):
             g = out["gen"][b].tolist()
@@ -285,7 +258,7 @@ def _run_golden(name, max_audio=256, max_text=64, max_gen=200, cases=None, batch
 def test_exact_engine_tiny_goldens_bitwise(name):
     """Parity mode reproduces the reference's own runs: every case's tokens and every
     step's full logit row bit for bit (free-running, no teacher forcing)."""
-    _need_gpu()
+    need_gpu()
     rep = _run_golden(name)
     assert all(r["tokens_equal"] for r in rep), rep
     assert all(r["logit_rows_equal"] == r["steps"] for r in rep), rep
@@ -293,14 +266,14 @@ def test_exact_engine_tiny_goldens_bitwise(name):
 
 def test_exact_engine_tiny_batched_bitwise():
     """Rows of a parity-mode batch are the reference's single-utterance runs, bitwise."""
-    _need_gpu()
+    need_gpu()
     rep = _run_golden("golden_tiny", batch=4)
     assert all(r["tokens_equal"] and r["logit_rows_equal"] == r["steps"] for r in rep), rep
 
 
 def test_exact_engine_mid_golden_bitwise():
     """2b-2b widths (d 2304, 8/4 heads of 256, FFN 9216, V 65541), 2+2 layers."""
-    _need_gpu()
+    need_gpu()
     rep = _run_golden("golden_mid", max_audio=256, max_text=64, max_gen=64)
     assert all(r["tokens_equal"] and r["logit_rows_equal"] == r["steps"] for r in rep), rep
 
@@ -308,7 +281,7 @@ def test_exact_engine_mid_golden_bitwise():
 def test_exact_engine_full_golden_bitwise():
     """Full depth (26+26 layers) at the C3 shapes (T_x 60, T_p 151), 16 steps per case:
     tokens and every step's logit-row sha equal the reference's."""
-    _need_gpu()
+    need_gpu()
     rep = _run_golden("golden_full", max_audio=200, max_text=64, max_gen=32, batch=2)
     assert all(r["tokens_equal"] and r["logit_rows_equal"] == r["steps"] for r in rep), rep
 
@@ -316,7 +289,7 @@ def test_exact_engine_full_golden_bitwise():
 def test_exact_engine_long_golden():
     """The C3 bench workload's first two rows to the full 751-token budget (L up to 903):
     the reference's tokens, and every step's logit-row sha."""
-    _need_gpu()
+    need_gpu()
     rep = _run_golden("golden_long", max_audio=1024, max_text=64, max_gen=760, batch=2)
     assert all(r["tokens_equal"] and r["logit_rows_equal"] == r["steps"] for r in rep), rep
 
@@ -326,7 +299,7 @@ def test_sdpa_expf_device_equals_glibc_restatement():
     host's glibc expf (oracle/glibc_expf.c, equal to libm on all 2^32 inputs) on 2^24 floats
     of (-104, 0] plus every input where glibc differs from the correctly rounded exp in a
     dense scan of (-1, 0]."""
-    _need_gpu()
+    need_gpu()
     from oracle import sdpa_emu as E
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -338,7 +311,7 @@ def test_sdpa_expf_device_equals_glibc_restatement():
     ref = E.expf(torch.from_numpy(x)).numpy()
     xd = torch.from_numpy(x).cuda()
     yd = torch.empty_like(xd)
-    assert L.t5g_sdpa_expf(C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()), x.size, _st()) == 0
+    assert L.t5g_sdpa_expf(C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()), x.size, stream()) == 0
     torch.cuda.synchronize()
     got = yd.cpu().numpy()
     bad = int((got.view(np.int32) != ref.view(np.int32)).sum())

@@ -3,33 +3,22 @@
 weights W_q -- held without a tolerance on the golden_mid config (true 2b-2b widths, 2 + 2
 layers), plus what the mode refuses. FP8 engines run the per-op launches at every batch size;
 the bf16 engine they are compared with runs its default launches."""
-import json
-import os
-
-import numpy as np
 import pytest
 import torch
+
+from tests.engine_cases import assert_same_run, both_loops, default_params, mid_config, need_gpu, utterances
 
 pytestmark = pytest.mark.gpu
 
 _STATE = {}
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs the MI355X")
-
-
 def _setup():
     """cfg, sd, the FP8 engine (A) and the bf16 engine on fp8_rounded_state_dict (B), once."""
     if not _STATE:
-        from conftest import GOLDEN as G
-        from t5gemma_tts_amd.config import named_config
         from t5gemma_tts_amd.engine import T5GemmaTTSEngine
-        from t5gemma_tts_amd.weights import fp8_rounded_state_dict, synthetic_weights
-        meta = json.load(open(os.path.join(G, "golden_mid.json")))
-        cfg = named_config(meta["config"], **meta["config_kw"])
-        sd = synthetic_weights(cfg, meta["weight_seed"])
+        from t5gemma_tts_amd.weights import fp8_rounded_state_dict
+        cfg, sd = mid_config()
         kw = dict(device="cuda:0", max_batch=20, max_text=64, max_audio=128, max_gen=40)
         _STATE["cfg"], _STATE["sd"], _STATE["kw"] = cfg, sd, kw
         _STATE["A"] = T5GemmaTTSEngine(cfg, sd, weight_format="fp8", **kw)
@@ -37,53 +26,30 @@ def _setup():
     return _STATE
 
 
-def _utts(cfg, n, seed):
-    from t5gemma_tts_amd.engine import Utterance
-    rng = np.random.default_rng(seed)
-    utts = []
-    for _ in range(n):
-        x = rng.integers(3, 4000, size=int(rng.integers(4, 40))).tolist()
-        tp = int(rng.integers(0, 40))
-        y = rng.integers(0, 65536, size=tp).tolist() + ([cfg.y_sep_token] if tp else [])
-        utts.append(Utterance(x=x, y=y, tgt_y_len=len(y) + int(rng.integers(8, 30))))
-    return utts
-
-
-def _params():
-    from t5gemma_tts_amd.engine import SamplingParams
-    return SamplingParams(top_k=30, top_p=0.9, temperature=0.8)
-
-
 def _both_loops(eng, utts, seeds):
-    """Tokens of the on-device graph loop, and tokens + every step's logits of the host loop on
-    the fast kernels."""
-    fast = eng.generate(utts, _params(), seeds=seeds)
-    host = eng.generate(utts, _params(), seeds=seeds, parity=True, exact=False, record_logits=True)
-    return fast, host
+    """(host, fast) of engine_cases.both_loops, the on-device graph loop run first."""
+    return both_loops(eng, utts, seeds, host_first=False)
 
 
-def _assert_same_run(a, b, B):
-    (fa, ha), (fb, hb) = a, b
-    for r in range(B):
-        assert fa["gen"][r].tolist() == fb["gen"][r].tolist(), r
-        assert ha["gen"][r].tolist() == hb["gen"][r].tolist(), r
-    assert len(ha["logits"]) == len(hb["logits"]) > 1
-    for s, (la, lb) in enumerate(zip(ha["logits"], hb["logits"])):
-        assert torch.equal(la.view(torch.int16), lb.view(torch.int16)), s
+def _assert_both_same(a, b, B):
+    (ha, fa), (hb, fb) = a, b
+    assert_same_run(fa, fb, B, "graph")
+    assert_same_run(ha, hb, B, "host")
+    assert len(ha["logits"]) > 1
     assert sum(len(g) for g in fa["gen"]) > B
 
 
 @pytest.mark.parametrize("B,fused", [(1, True), (8, True), (16, True), (8, False), (20, False)])
 def test_fp8_engine_is_bitwise_the_bf16_fast_path_on_rounded_weights(B, fused):
-    _need_gpu()
+    need_gpu()
     st = _setup()
-    utts = _utts(st["cfg"], B, 90 + B)
+    utts = utterances(st["cfg"], B, 90 + B)
     seeds = list(range(700, 700 + B))
     try:
         st["A"].set_fused(fused)
         st["B"].set_fused(fused)
         launches = st["A"].block_launches()
-        _assert_same_run(_both_loops(st["A"], utts, seeds), _both_loops(st["B"], utts, seeds), B)
+        _assert_both_same(_both_loops(st["A"], utts, seeds), _both_loops(st["B"], utts, seeds), B)
         assert st["A"].block_launches() == launches   # FP8 mode: per-op launches only
     finally:
         st["A"].set_fused(True)
@@ -91,16 +57,16 @@ def test_fp8_engine_is_bitwise_the_bf16_fast_path_on_rounded_weights(B, fused):
 
 
 def test_fp8_engine_is_not_bf16_in_disguise():
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.engine import T5GemmaTTSEngine
     st = _setup()
     assert st["A"].native_weight_format() == "fp8" and st["B"].native_weight_format() == "bf16"
-    utts = _utts(st["cfg"], 8, 31)
+    utts = utterances(st["cfg"], 8, 31)
     seeds = list(range(40, 48))
-    a = st["A"].generate(utts, _params(), seeds=seeds, parity=True, exact=False, record_logits=True)
+    a = st["A"].generate(utts, default_params(), seeds=seeds, parity=True, exact=False, record_logits=True)
     raw = T5GemmaTTSEngine(st["cfg"], st["sd"], shared_from=None, **st["kw"])
     try:
-        r = raw.generate(utts, _params(), seeds=seeds, parity=True, exact=False, record_logits=True)
+        r = raw.generate(utts, default_params(), seeds=seeds, parity=True, exact=False, record_logits=True)
     finally:
         raw.close()
     la, lr = a["logits"][0], r["logits"][0]
@@ -112,32 +78,32 @@ def test_fp8_handoff_poison_reruns_on_per_op_launches():
     """As test_handoff_timeout_falls_back_to_per_op_launches, on an FP8 engine: the sticky
     timeout word makes t5g_read_tokens report T5G_EHANDOFF, engine.generate reruns the call
     with set_fused(False) -- the same tokens -- and the next call is clean again."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     st = _setup()
     eng = st["A"]
-    utts = _utts(st["cfg"], 8, 77)
+    utts = utterances(st["cfg"], 8, 77)
     seeds = list(range(500, 508))
-    ref = eng.generate(utts, _params(), seeds=seeds)
+    ref = eng.generate(utts, default_params(), seeds=seeds)
     _lib.check(_lib.lib().t5g_engine_poison_handoff(eng.h, 99), "poison_handoff")
     with pytest.warns(UserWarning):
-        out = eng.generate(utts, _params(), seeds=seeds)
-    again = eng.generate(utts, _params(), seeds=seeds)
+        out = eng.generate(utts, default_params(), seeds=seeds)
+    again = eng.generate(utts, default_params(), seeds=seeds)
     for b in range(8):
         assert out["gen"][b].tolist() == ref["gen"][b].tolist(), b
         assert again["gen"][b].tolist() == ref["gen"][b].tolist(), b
 
 
 def test_fp8_refusals():
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import T5GemmaTTSEngine
     from t5gemma_tts_amd.weights import synthetic_weights
     st = _setup()
-    utts = _utts(st["cfg"], 1, 5)
+    utts = utterances(st["cfg"], 1, 5)
     with pytest.raises(ValueError):
-        st["A"].generate(utts, _params(), seeds=[1], parity=True)
+        st["A"].generate(utts, default_params(), seeds=[1], parity=True)
     with pytest.raises(ValueError):
         st["A"].set_exact(True)
     assert _lib.lib().t5g_engine_set_exact(st["A"].h, 1, _lib.gelu_erf_table(), _lib.EXACT_THREADS) \
@@ -153,8 +119,8 @@ def test_fp8_refusals():
     twin = T5GemmaTTSEngine(st["cfg"], {}, shared_from=st["A"], weight_format="fp8", **st["kw"])
     try:
         assert twin.native_weight_format() == "fp8"
-        a = st["A"].generate(utts, _params(), seeds=[9])
-        b = twin.generate(utts, _params(), seeds=[9])
+        a = st["A"].generate(utts, default_params(), seeds=[9])
+        b = twin.generate(utts, default_params(), seeds=[9])
         assert a["gen"][0].tolist() == b["gen"][0].tolist()
     finally:
         twin.close()

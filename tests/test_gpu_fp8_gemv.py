@@ -7,25 +7,13 @@ import ctypes as C
 import pytest
 import torch
 
-from test_fp8_cpu import planted_matrix
+from tests.engine_cases import need_gpu, ptr, stream
+from tests.fixture_cases import planted_matrix
 
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
 DEV = "cuda:0"
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
 
 
 def _quantize(W, want_wq=True):
@@ -37,14 +25,14 @@ def _quantize(W, want_wq=True):
     p8 = torch.full((L.t5g_fp8_packed_bytes(N, K),), 0x55, dtype=torch.uint8, device=DEV)
     scale = torch.full((-(-N // 16) * 16,), -7.0, dtype=torch.float32, device=DEV)
     wq = torch.full((N, K), 9.0, dtype=BF16, device=DEV) if want_wq else None
-    rc = L.t5g_quantize_weight_fp8(_p(Wd), N, K, K, _p(p8), _p(scale), _p(wq), _stream())
+    rc = L.t5g_quantize_weight_fp8(ptr(Wd), N, K, K, ptr(p8), ptr(scale), ptr(wq), stream(DEV))
     return rc, p8, scale, wq
 
 
 def _unpack(p8, scale, N, K):
     from t5gemma_tts_amd import _lib
     out = torch.full((N, K), 9.0, dtype=BF16, device=DEV)
-    _lib.check(_lib.lib().t5g_fp8_unpack(_p(p8), _p(scale), N, K, _p(out), _stream()), "fp8_unpack")
+    _lib.check(_lib.lib().t5g_fp8_unpack(ptr(p8), ptr(scale), N, K, ptr(out), stream(DEV)), "fp8_unpack")
     torch.cuda.synchronize()
     return out
 
@@ -57,7 +45,7 @@ def test_all_codes_round_trip_through_the_kernels_convert():
     """16 rows x 256: row r holds every finite e4m3 value (the two NaN slots 0) times 2^e_r.
     Quantise, then unpack through the kernels' own convert: the input, bit for bit -- every
     code, subnormals included, and each row scale as the convert's scale operand."""
-    _need_gpu()
+    need_gpu()
     vals = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float()
     vals[0x7F] = 0.0
     vals[0xFF] = 0.0
@@ -73,7 +61,7 @@ def test_all_codes_round_trip_through_the_kernels_convert():
 
 @pytest.mark.parametrize("N,K", [(40, 96), (208, 2304)])
 def test_device_quantiser_equals_the_restatement(N, K):
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.weights import quantize_fp8_rows
     W = planted_matrix(N, K, 11 + N)
     codes, scale_ref, wq_ref = quantize_fp8_rows(W)
@@ -96,7 +84,7 @@ def test_device_quantiser_equals_the_restatement(N, K):
 
 
 def test_device_quantiser_refuses_a_non_finite_weight():
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     W = planted_matrix(40, 96, 5)
     W[17, 40] = float("inf")
@@ -127,7 +115,7 @@ def _weights(N, K):
         rc, p8, scale, wq = _quantize(W)
         assert rc == 0
         p16 = torch.zeros(L.t5g_packed_bytes(N, K) // 2, dtype=BF16, device=DEV)
-        _lib.check(L.t5g_pack_weight(_p(wq), N, K, K, _p(p16), _stream()), "pack")
+        _lib.check(L.t5g_pack_weight(ptr(wq), N, K, K, ptr(p16), stream(DEV)), "pack")
         _W[(N, K)] = (p8, scale, p16)
     return _W[(N, K)]
 
@@ -144,17 +132,17 @@ def _run(fp8, epi, M, N, K, splits, nw, un, X, bias, max_grid=0):
     a.bias = bias.data_ptr() if bias is not None else None
     if fp8:
         a.W = p8.data_ptr()
-        _lib.check(L.t5g_gemv_fp8(C.byref(a), _p(scale), _stream()), "gemv_fp8")
+        _lib.check(L.t5g_gemv_fp8(C.byref(a), ptr(scale), stream(DEV)), "gemv_fp8")
     else:
         a.W = p16.data_ptr()
-        _lib.check(L.t5g_gemv(C.byref(a), _stream()), "gemv")
+        _lib.check(L.t5g_gemv(C.byref(a), stream(DEV)), "gemv")
     torch.cuda.synchronize()
     return Y.cpu()
 
 
 @pytest.mark.parametrize("epi,K,N,splits,nw,un,M", [c[:6] + (m,) for c in GEMV_CASES for m in c[6]])
 def test_gemv_fp8_bitwise_equals_bf16_gemv_on_wq(epi, K, N, splits, nw, un, M):
-    _need_gpu()
+    need_gpu()
     g = torch.Generator().manual_seed(1000 + M + K)
     X = torch.randn(M, K, generator=g).to(BF16).to(DEV)
     bias = (torch.randn(N, generator=g) * 0.1).to(BF16).to(DEV) if epi == 1 else None

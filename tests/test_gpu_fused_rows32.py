@@ -13,53 +13,23 @@ import functools
 import os
 import re
 
-import numpy as np
 import pytest
-import torch
 
-from conftest import GOLDEN, REPO
+from conftest import REPO
+from tests.engine_cases import assert_same_run, default_params, mid_engine, need_gpu, utterances
 
 gpu = pytest.mark.gpu
 
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs the MI355X")
+# ragged rows as engine_cases.utterances makes them; row 0 has no prompt, row 1 has 64 text keys
+# (the most the launch's cross attention reads), row 2 has 4
+ROWS = dict(bare_first=True, text_lens={1: 64, 2: 4})
 
 
 @functools.lru_cache(maxsize=None)
-def _mid_engine(max_audio):
-    """tests/test_gpu_fused.py::_mid_engine(32) (golden_mid at the true widths, 2 + 2 layers,
+def _engine(max_audio):
+    """engine_cases.mid_engine(32, max_audio) (golden_mid at the true widths, 2 + 2 layers,
     max_text 64), shared by the tests of one cache size."""
-    import json
-    from t5gemma_tts_amd.config import named_config
-    from t5gemma_tts_amd.engine import T5GemmaTTSEngine
-    from t5gemma_tts_amd.weights import synthetic_weights
-    meta = json.load(open(os.path.join(GOLDEN, "golden_mid.json")))
-    cfg = named_config(meta["config"], **meta["config_kw"])
-    sd = synthetic_weights(cfg, meta["weight_seed"])
-    eng = T5GemmaTTSEngine(cfg, sd, device="cuda:0", max_batch=32, max_text=64, max_audio=max_audio, max_gen=40)
-    return cfg, eng
-
-
-def _utts(cfg, n, seed, tp_max=40):
-    """Ragged rows as tests/test_gpu_fused.py::_utts makes them; row 0 has no prompt, row 1 has
-    64 text keys (the most the launch's cross attention reads), row 2 has 4."""
-    from t5gemma_tts_amd.engine import Utterance
-    rng = np.random.default_rng(seed)
-    utts = []
-    for i in range(n):
-        nx = 64 if i == 1 else 4 if i == 2 else int(rng.integers(4, 40))
-        x = rng.integers(3, 4000, size=nx).tolist()
-        tp = 0 if i == 0 else int(rng.integers(0, tp_max))
-        y = rng.integers(0, 65536, size=tp).tolist() + ([cfg.y_sep_token] if tp else [])
-        utts.append(Utterance(x=x, y=y, tgt_y_len=len(y) + int(rng.integers(8, 30))))
-    return utts
-
-
-def _params():
-    from t5gemma_tts_amd.engine import SamplingParams
-    return SamplingParams(top_k=30, top_p=0.9, temperature=0.8)
+    return mid_engine(32, max_audio)
 
 
 def _run(eng, utts, seeds):
@@ -71,30 +41,21 @@ def _run(eng, utts, seeds):
         # a hand-off that gave up would rerun the call on the per-op launches (the same
         # tokens): here that is a failure of the launch under test, not a fallback to accept
         warnings.simplefilter("error")
-        host = eng.generate(utts, _params(), seeds=seeds, parity=True, exact=False, record_logits=True)
+        # not engine_cases.both_loops: the placement is read between the two loops
+        host = eng.generate(utts, default_params(), seeds=seeds, parity=True, exact=False, record_logits=True)
         mode = eng.attn_in_block_mode()
-        fast = eng.generate(utts, _params(), seeds=seeds)
+        fast = eng.generate(utts, default_params(), seeds=seeds)
     return host, fast, eng.block_launches() - b0, eng.attn_in_block_launches() - s0, mode
-
-
-def _assert_same(a, b, B, tag):
-    for r in range(B):
-        assert a["gen"][r].tolist() == b["gen"][r].tolist(), (tag, r)
-    if "logits" not in a:   # the graph-replayed loop: tokens only
-        return
-    assert len(a["logits"]) == len(b["logits"]), tag
-    for s, (la, lb) in enumerate(zip(a["logits"], b["logits"])):
-        assert torch.equal(la.view(torch.int16), lb.view(torch.int16)), (tag, s)
 
 
 @gpu
 @pytest.mark.parametrize("B", [17, 20, 25, 26, 32])
 def test_block_rows32_bitwise_equal_to_per_op_launches(B):
-    _need_gpu()
-    cfg, eng = _mid_engine(128)
+    need_gpu()
+    cfg, eng = _engine(128)
     eng.set_block_max_rows(32)
     eng.set_attn_in_block(2)
-    utts = _utts(cfg, B, 140 + B)
+    utts = utterances(cfg, B, 140 + B, **ROWS)
     seeds = list(range(700, 700 + B))
     L = cfg.backbone.num_decoder_layers
     runs = []
@@ -105,8 +66,8 @@ def test_block_rows32_bitwise_equal_to_per_op_launches(B):
     finally:
         eng.set_fused(True)
     for k in (1, 2):
-        _assert_same(runs[0][0], runs[k][0], B, ("host", k))
-        _assert_same(runs[0][1], runs[k][1], B, ("graph", k))
+        assert_same_run(runs[0][0], runs[k][0], B, ("host", k))
+        assert_same_run(runs[0][1], runs[k][1], B, ("graph", k))
     # the whole-layer launch ran in the fused runs (one per layer and captured step at least)
     # and not in the per-op run
     assert runs[0][2] >= L and runs[2][2] >= L and runs[1][2] == 0, [r[2] for r in runs]
@@ -122,11 +83,11 @@ def test_block_rows32_bitwise_equal_to_per_op_launches(B):
     (32, 960, 2, 0),                      # 15 chunks: 1 920 slots > 1 536 -- S as its own launch
 ])
 def test_block_rows32_attention_in_block(B, max_audio, mode, expect):
-    _need_gpu()
-    cfg, eng = _mid_engine(max_audio)
+    need_gpu()
+    cfg, eng = _engine(max_audio)
     eng.set_block_max_rows(32)
     eng.set_fused(True)
-    utts = _utts(cfg, B, 30 + B + max_audio, tp_max=max_audio - 45)
+    utts = utterances(cfg, B, 30 + B + max_audio, tp_max=max_audio - 45, **ROWS)
     seeds = list(range(B))
     L = cfg.backbone.num_decoder_layers
     try:
@@ -139,8 +100,8 @@ def test_block_rows32_attention_in_block(B, max_audio, mode, expect):
     assert m_on == expect and m_off == 0, (m_on, m_off)
     assert (ns_on > 0) == (expect != 0) and ns_off == 0, (ns_on, ns_off)   # S ran exactly where expected
     assert nb_on >= L and nb_off >= L, (nb_on, nb_off)                     # the whole-layer launch ran either way
-    _assert_same(on, off, B, "on/off")
-    _assert_same(fon, foff, B, "graph on/off")
+    assert_same_run(on, off, B, "on/off")
+    assert_same_run(fon, foff, B, "graph on/off")
     assert sum(len(g) for g in on["gen"]) > B
 
 
@@ -148,21 +109,21 @@ def test_block_rows32_attention_in_block(B, max_audio, mode, expect):
 def test_block_rows32_rows_are_independent():
     """Rows 0, 16 and 31 of a 32-row call (the first row of each tile and the last row) give
     the tokens of the same utterances run alone with the same seeds."""
-    _need_gpu()
-    cfg, eng = _mid_engine(128)
+    need_gpu()
+    cfg, eng = _engine(128)
     eng.set_block_max_rows(32)
     eng.set_fused(True)
     eng.set_attn_in_block(2)
-    utts = _utts(cfg, 32, 91)
+    utts = utterances(cfg, 32, 91, **ROWS)
     seeds = list(range(40, 72))
     import warnings
     b0 = eng.block_launches()
     with warnings.catch_warnings():
         warnings.simplefilter("error")   # no rerun on the per-op launches (see _run)
-        full = eng.generate(utts, _params(), seeds=seeds)
+        full = eng.generate(utts, default_params(), seeds=seeds)
         assert eng.block_launches() - b0 >= cfg.backbone.num_decoder_layers
         for r in (0, 16, 31):
-            alone = eng.generate([utts[r]], _params(), seeds=[seeds[r]])
+            alone = eng.generate([utts[r]], default_params(), seeds=[seeds[r]])
             assert alone["gen"][0].tolist() == full["gen"][r].tolist(), r
 
 

@@ -6,21 +6,13 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.engine_cases import need_gpu
+from tests.kernel_cases import EPS
+from tests.kernel_cases import rms_norm as _rms
+
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
-EPS = 1e-6
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _rms(x, w):
-    xf = x.float()
-    r = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + EPS)
-    return ((xf * r) * (1.0 + w.float())).to(BF16)
 
 
 def _epilogue(acc, epi, bias):
@@ -87,7 +79,7 @@ def _run(epi, M, N, K, nw, splits, seed, max_grid=0, X=None, W=None, layout=0):
 
 @pytest.mark.parametrize("epi,M,N,K,nw,splits", CASES)
 def test_gemv_vs_fp32(epi, M, N, K, nw, splits):
-    _need_gpu()
+    need_gpu()
     got, X, W, bias = _run(epi, M, N, K, nw, splits, seed=M * 7 + N + K + splits)
     ref = _epilogue(X.float() @ W.float().t(), epi, bias)
     if epi == 4:
@@ -104,7 +96,7 @@ def test_gemv_stream_tail_regression():
     into the staged X rows other waves were still reading. Deterministic guard: grid caps
     that leave blocks with nu = 4 / 5 / 11 / 12 units (not multiples of 2*UN) on the
     gate/up shape, each launch compared with the fp32 reference and the uncapped launch."""
-    _need_gpu()
+    need_gpu()
     M, N, K = 8, 18432, 2304
     full, X, W, bias = _run(3, M, N, K, 8, 1, seed=11)
     ref = _epilogue(X.float() @ W.float().t(), 3, bias)
@@ -116,7 +108,7 @@ def test_gemv_stream_tail_regression():
 
 def test_gemv_batch_invariant():
     """Row m of an M-row launch equals the same row run alone (bitwise)."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     dev = "cuda"
@@ -148,7 +140,7 @@ def test_gemv_batch_invariant():
 def test_gemv_register_x_variant(epi, M):
     """layout 1 (register-resident X, 1..32 rows, K = 2304): vs the fp32 reference, and
     bitwise equal to the LDS-staged kernel on every 16-row slice of the batch."""
-    _need_gpu()
+    need_gpu()
     N, K = (18432, 2304) if epi == 3 else (6000, 2304)
     g = torch.Generator(device="cpu").manual_seed(M + epi)
     W = (torch.randn(N, K, generator=g) * 0.02).to(BF16)
@@ -171,7 +163,7 @@ def test_gemv_register_x_wave_counts(nw, M, epi):
     65 541-row head 8 waves up to 16 rows, 4 waves -- the partial-sum buffer's LDS limit --
     up to 32): vs the fp32 reference, and batch-invariant (every row bitwise equal to the
     same row alone)."""
-    _need_gpu()
+    need_gpu()
     N, K = (18432, 2304) if epi == 3 else (65541, 2304)
     g = torch.Generator(device="cpu").manual_seed(nw * 31 + M)
     W = (torch.randn(N, K, generator=g) * 0.02).to(BF16)
@@ -192,7 +184,7 @@ def test_gemv_register_x_split_k(nw, M):
     """layout 1 over 8 k-slices of K = 9216 (the decode down projection: fp32 slabs, 32
     blocks per slice each streaming several units): slab sum vs the fp32 reference, and
     batch-invariant."""
-    _need_gpu()
+    need_gpu()
     N, K, S = 2304, 9216, 8
     g = torch.Generator(device="cpu").manual_seed(nw * 7 + M)
     W = (torch.randn(N, K, generator=g) * 0.02).to(BF16)
@@ -210,7 +202,7 @@ def test_resid_norm_vs_fp32(M):
     """The decode step's residual + RMSNorm kernel (t5g_resid_norm; norm.hip): against a
     PyTorch fp32 restatement of [tf] T5GemmaRMSNorm :61-78 wired as the residual add of
     PMDecoderLayer :285-323 -- within the bf16 roundings of the two norms."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     dev = "cuda"
@@ -245,7 +237,7 @@ def test_gemv_register_x_grid_invariant(epi, K, splits, nw, M, caps):
     """The register-X GEMV's results do not depend on how many blocks share the units (a
     unit's sums are one block's fixed wave order): bitwise equal at the default grid (one
     block per CU per slice) and at capped grids, e.g. a partitioned GPU with fewer CUs."""
-    _need_gpu()
+    need_gpu()
     N = 18432 if epi == 3 else (65541 if epi == 1 else 2304)
     g = torch.Generator(device="cpu").manual_seed(K + splits + M)
     W = (torch.randn(N, K, generator=g) * 0.02).to(BF16)

@@ -21,15 +21,11 @@ import pytest
 import torch
 
 from conftest import REPO
+from tests.engine_cases import need_gpu
 
 pytestmark = pytest.mark.gpu
 STEPS = 100
 RTOL = 0.03        # the fast path's tolerance (test_gpu_parity_full.py)
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def _row(cfg, seed):
@@ -42,7 +38,7 @@ def _row(cfg, seed):
 
 @pytest.mark.timeout(1500)
 def test_fast_path_error_vs_fp64_noise_floor():
-    _need_gpu()
+    need_gpu()
     from oracle.t5g_oracle import SamplerParams as OP
     from oracle.t5g_oracle import T5GemmaTTSOracle, draw_noise, sample_helper
     from t5gemma_tts_amd.config import config_2b2b

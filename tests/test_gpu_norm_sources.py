@@ -15,13 +15,13 @@ import torch
 
 from oracle.t5g_oracle import inv_freq_table
 from tests import kernel_cases as kc
-from tests.kernel_cases import BF16, SENT
+from tests.engine_cases import need_gpu
+from tests.kernel_cases import BF16, EPS, SENT
 from tests.kernel_cases import bf16_step as _bf16_step
 from tests.kernel_cases import i16 as _i16
+from tests.kernel_cases import rms_norm as _rms
 from tests.kernel_cases import sentinel as _sentinel
 from tests.kernel_cases import trig_safe as _trig_safe
-from tests.test_gpu_attention import _need_gpu
-from tests.test_gpu_gemv import EPS, _rms
 
 pytestmark = pytest.mark.gpu
 
@@ -117,7 +117,7 @@ def _close(pairs, label, exact_first=False):
 def test_widths(M, d):
     """d = 8, 128, 2304, 8192: 63, 48, 32 and 0 idle threads in blocks of 64, 64, 320 and 1 024;
     the full residual + two-norm form on the delta source."""
-    _need_gpu()
+    need_gpu()
     h, xn, rh, rxn, _ = _case(d + M, M, d)
     _close([(h, rh), (xn, rxn)], f"delta M={M} d={d}")
 
@@ -127,7 +127,7 @@ def test_ids_source(d):
     """v = bf16(table[ids[m]] * scale) from a table of 300 rows (in-range ids, first and last
     row among them): as the layer-0 embedding launch (no post norm, no residual: h is the
     scaled row itself, bit-exact), and in the full form."""
-    _need_gpu()
+    need_gpu()
     h, xn, rh, rxn, _ = _case(100 + d, 5, d, src="ids", post=False, resid=False)
     _close([(h, rh), (xn, rxn)], f"ids embed d={d}", exact_first=True)
     h, xn, rh, rxn, _ = _case(200 + d, 33, d, src="ids")
@@ -139,7 +139,7 @@ def test_part_source(nsplit):
     """v = bf16(part[0] + part[1] + ...) over fp32 slabs with ldp > d, added in slab order in
     fp32: with no post norm and no residual, h is that sum, bit-exact, on values whose sum
     depends on the order. Then the full form."""
-    _need_gpu()
+    need_gpu()
     for M, d in ((5, 2304), (33, 8), (3, 8192)):
         h, xn, rh, rxn, ex = _case(300 + nsplit + d, M, d, src="part", nsplit=nsplit, post=False, resid=False)
         if nsplit > 2:   # teeth, from the reference alone: the launch's own slabs, added in reverse, give other bits
@@ -153,7 +153,7 @@ def test_part_source(nsplit):
 def test_absent_operands(d):
     """Every combination of post_w / resid / pre_w present or absent that resid_norm() accepts:
     all eight with resid_out, and the four with pre_w where only normed_out is written."""
-    _need_gpu()
+    need_gpu()
     n = 0
     for post, resid, pre, want_h in itertools.product((True, False), repeat=4):
         if not want_h and not pre:
@@ -171,7 +171,7 @@ def test_out_rows():
     """A subset of 33 source rows, written compact: the source, the ids and resid are read at
     the source row, the outputs written at the compact row. Also the engine's gather form
     (delta source, nothing else: a bit-exact row copy)."""
-    _need_gpu()
+    need_gpu()
     rows = [31, 0, 7, 32, 16]
     for src in ("delta", "ids"):
         h, xn, rh, rxn, _ = _case(600, 5, 2304, src=src, out_rows=rows)
@@ -188,7 +188,7 @@ def test_side_written_rope_table(M, d, rope_D):
     rope_tab[i] (d = 8: 64 threads loop over 128 frequencies). Against fp64 cos / sin of the
     fp32 angle, with tests/test_gpu_rope_store.py's safe-set rule: bit-equal where cos and sin
     are more than 4 fp32 ulps from a bf16 tie, a neighbouring bf16 value elsewhere."""
-    _need_gpu()
+    need_gpu()
     h, xn, rh, rxn, ex = _case(700 + d, M, d, rope_D=rope_D)
     _close([(h, rh), (xn, rxn)], f"rope side output M={M} d={d}")
     tab = ex["tab"]

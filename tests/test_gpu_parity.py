@@ -8,22 +8,11 @@ import pytest
 import torch
 
 from conftest import GOLDEN, REPO
+from tests.engine_cases import golden_params, load_golden, need_gpu, teacher_forced_check, topk_agree
 
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name + ".json")) as f:
-        meta = json.load(f)
-    npz = os.path.join(GOLDEN, name + ".npz")
-    return meta, (dict(np.load(npz)) if os.path.exists(npz) else {})
 
 
 def _bf16_from_bits(a):
@@ -45,7 +34,7 @@ PREFILL = 0x100   # include/t5gtts.h T5G_GEMM_PREFILL: the encoder / prefill ker
     (37, 300, 128, 1 | PREFILL, 1), (130, 2304, 2304, 2 | PREFILL, 1), (5, 200, 96, PREFILL, 1),
 ])
 def test_gemm_p16_vs_fp32(M, N, K, epi, splits):
-    _need_gpu()
+    need_gpu()
     flags, epi = epi & ~0xff, epi & 0xff
     import ctypes as C
     from t5gemma_tts_amd import _lib
@@ -110,7 +99,7 @@ def test_gemm_p16_vs_fp32(M, N, K, epi, splits):
 def test_gemm_decode_rows_bitwise_across_kernels():
     """The 17..32-row decode GEMM (X staged in LDS, gemm_dx_kernel) keeps the k-slice order
     of the 1..16-row kernel: rows 0..7 of a 32-row launch equal an 8-row launch bitwise."""
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -134,7 +123,7 @@ def test_gemm_decode_rows_bitwise_across_kernels():
 def test_gemm_prefill_batch_invariant():
     """Many-token kernel: a token's outputs do not depend on the other tokens of the launch
     (bitwise) -- rows 37..73 of a 300-token launch equal the same rows launched alone."""
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
@@ -165,57 +154,6 @@ def _engine(cfg, sd, **kw):
     return T5GemmaTTSEngine(cfg, sd, device="cuda:0", **kw)
 
 
-def _params(c):
-    from t5gemma_tts_amd.engine import SamplingParams
-    return SamplingParams(top_k=c["top_k"], top_p=c["top_p"], min_p=c["min_p"], temperature=c["temperature"],
-                          stop_repetition=c["stop_repetition"], silence_tokens=tuple(c["silence_tokens"]))
-
-
-def teacher_forced_check(cfg, sd, utt, params_o, seed, gpu_out, rtol):
-    """Replay the GPU's token sequence through the CPU oracle. At every step:
-    (a) the reference sampler fed the GPU's logits + the same noise returns the GPU's
-        token (sampler exactness, incl. tie order and stop rules);
-    (b) the GPU logits match the oracle logits under the identical history
-        (bf16 GEMM accumulation order => within a few bf16 ulps, rtol of max |logit|).
-    Returns (max relative logit error, number of exactly equal logit rows)."""
-    import copy
-    from oracle.t5g_oracle import T5GemmaTTSOracle, draw_noise, sample_helper
-    orc = T5GemmaTTSOracle(cfg, sd)
-    ctx = orc.prepare(utt.x, utt.y, utt.tgt_y_len)
-    st = ctx["state"]
-    gen = torch.Generator().manual_seed(int(seed))
-    toks = gpu_out["gen"][0].tolist()
-    worst, exact_rows = 0.0, 0
-    for t, tok in enumerate(toks):
-        lo = orc.step_logits(ctx)
-        lg = gpu_out["logits"][t][0].cpu()
-        noise = draw_noise(gen, lo.shape[-1])
-        scale = lo.float().abs().max().item()
-        err = (lg.float() - lo.float()).abs().max().item() / max(scale, 1e-6)
-        worst = max(worst, err)
-        exact_rows += int(torch.equal(lg, lo))
-        st_g = copy.deepcopy(st)
-        tok_g, _ = sample_helper(lg.clone(), params_o, st_g, noise, eos=cfg.eog_inference,
-                                 encodec_sr=cfg.encodec_sr, extra_cutoff=cfg.extra_cutoff,
-                                 text_guard_frames_per_token=cfg.text_guard_frames_per_token)
-        assert tok_g == tok, f"step {t}: reference sampler on GPU logits -> {tok_g}, GPU sampled {tok}"
-        ctx["state"] = st = st_g
-        st.cur_num_gen += 1
-        st.current_length += 1
-        if tok == cfg.eog_inference:
-            assert t == len(toks) - 1
-            break
-        orc.advance(ctx, tok)
-    assert worst <= rtol, worst
-    return worst, exact_rows
-
-
-def _oparams(c):
-    from oracle.t5g_oracle import SamplerParams
-    return SamplerParams(top_k=c["top_k"], top_p=c["top_p"], min_p=c["min_p"], temperature=c["temperature"],
-                         stop_repetition=c["stop_repetition"], silence_tokens=tuple(c["silence_tokens"]))
-
-
 # free-running token-exact cases each golden set must keep (measured on MI355X, see
 # profiles/r02_parity_rates.json); every other case must diverge only at an explained
 # sampling-boundary flip (see _explain_divergence)
@@ -231,15 +169,6 @@ MIN_EXACT = {"golden_tiny": 12, "golden_tiny_eager": 2, "golden_tiny_window": 4}
 # measured 1.36 % (round 4-5), so a further drift of the fast kernels' softcap path fails here
 # rather than only through token flips
 TF_RTOL = {"golden_tiny": 0.02, "golden_tiny_eager": 0.016, "golden_tiny_window": 0.02}
-
-
-def _topk_agree(g, r, k, tol):
-    gv, gi = torch.topk(g.float(), k)
-    rv, ri = torch.topk(r.float(), k)
-    cut = min(gv[-1].item(), rv[-1].item())
-    sg = {int(i) for i, v in zip(gi, gv) if v.item() > cut + tol}
-    sr = {int(i) for i, v in zip(ri, rv) if v.item() > cut + tol}
-    return sg <= set(ri.tolist()) and sr <= set(gi.tolist())
 
 
 def _explain_divergence(cfg, c, gpu_logits, ref_logits, t, gpu_tok, oparams):
@@ -279,13 +208,13 @@ def test_tiny_engine_vs_reference_golden(name):
     (b) per-step top-k candidate sets agree with the reference's (ties within tolerance);
     (c) free-running token equality with the reference on >= MIN_EXACT[name] cases, and
         every other case diverges only at an explained sampling-boundary flip."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
     if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
         pytest.skip("fixture missing")
-    meta, arrs = _load(name)
+    meta, arrs = load_golden(name)
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     eng = _engine(cfg, sd, max_batch=8, max_text=64, max_audio=256, max_gen=200)
@@ -295,9 +224,9 @@ def test_tiny_engine_vs_reference_golden(name):
         u = Utterance(x=c["x"], y=c["y"], tgt_y_len=c["tgt"])
         # the tiny eager (softcap) configuration: the reference RNG and sampler with the fast
         # kernels (parity mode restates eager attention for the 2b-2b call shape only)
-        out = eng.generate([u], _params(c), seeds=[c["seed"]], parity=True, record_logits=True,
+        out = eng.generate([u], golden_params(c), seeds=[c["seed"]], parity=True, record_logits=True,
                            exact=False if name == "golden_tiny_eager" else None)
-        w, ex = teacher_forced_check(cfg, sd, u, _oparams(c), c["seed"], out, rtol=TF_RTOL[name])
+        w, ex = teacher_forced_check(cfg, sd, u, golden_params(c, oracle=True), c["seed"], out, rtol=TF_RTOL[name])
         worst = max(worst, w)
         rows_exact += ex
         rows += len(out["gen"][0])
@@ -310,12 +239,13 @@ def test_tiny_engine_vs_reference_golden(name):
         n_cmp = len(g) if t_div is None else t_div + 1
         for t in range(min(n_cmp, ref.shape[0], len(got))):
             topk_n += 1
-            topk_ok += int(_topk_agree(got[t], ref[t], 30, 0.02 * ref[t].float().abs().max().item()))
+            topk_ok += int(topk_agree(got[t], ref[t], 30, 0.02 * ref[t].float().abs().max().item()))
         if t_div is None:
             exact_tokens += 1
             assert len(got) == ref.shape[0]
         else:
-            ok, info = _explain_divergence(cfg, c, got[t_div], ref[t_div], t_div, g[t_div], _oparams(c))
+            ok, info = _explain_divergence(cfg, c, got[t_div], ref[t_div], t_div, g[t_div],
+                                           golden_params(c, oracle=True))
             info["case"] = ci
             divergences.append(info)
             assert ok, info
@@ -332,7 +262,7 @@ def test_tiny_engine_vs_reference_golden(name):
 
 def test_batched_rows_equal_single_rows():
     """Row i of a batch == the same utterance run alone (tokens and logits bitwise)."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
@@ -360,7 +290,7 @@ def test_batch32_rows_equal_single_rows():
     """At B = 32 (C5; decode GEMMs on the tiled kernel instead of the <= 16-row GEMV) rows
     of a 32-row batch equal the same utterances run alone (tokens bitwise), on the
     on-device sampler."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
@@ -386,7 +316,7 @@ def test_out_of_range_ids_raise_before_any_launch():
     """Text ids >= the text vocabulary and prompt codes >= the audio vocabulary raise
     IndexError (the reference's nn.Embedding does) instead of reaching the embedding
     gathers; the engine keeps working afterwards."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
@@ -403,7 +333,7 @@ def test_out_of_range_ids_raise_before_any_launch():
 
 def test_graph_fast_path_matches_eager_launches():
     """hipGraph replay == plain launches (production Philox noise, same seeds)."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
@@ -423,22 +353,22 @@ def test_graph_fast_path_matches_eager_launches():
 def test_mid_width_teacher_forced():
     """True 2b-2b widths (d 2304, 8x256 heads, FFN 9216, V 65541), 2+2 layers: GPU vs
     CPU oracle teacher-forced, batch of 2 with a voice-clone prompt."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
-    meta, _ = _load("golden_mid")
+    meta, _ = load_golden("golden_mid")
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     eng = _engine(cfg, sd, max_batch=2, max_text=64, max_audio=128, max_gen=64)
     cases = meta["cases"]
     utts = [Utterance(x=c["x"], y=c["y"], tgt_y_len=c["tgt"]) for c in cases]
-    out = eng.generate(utts, [_params(c) for c in cases], seeds=[c["seed"] for c in cases], parity=True,
+    out = eng.generate(utts, [golden_params(c) for c in cases], seeds=[c["seed"] for c in cases], parity=True,
                        record_logits=True)
     n_exact = 0
     for b, c in enumerate(cases):
         one = {"gen": [out["gen"][b]], "logits": [[l[b]] for l in out["logits"]]}
-        w, ex = teacher_forced_check(cfg, sd, utts[b], _oparams(c), c["seed"], one, rtol=0.02)
+        w, ex = teacher_forced_check(cfg, sd, utts[b], golden_params(c, oracle=True), c["seed"], one, rtol=0.02)
         n_exact += int(out["gen"][b].tolist() == c["gen"])
         print(f"mid row {b}: max rel logit err {w:.3g}, bit-identical rows {ex}/{len(out['gen'][b])}")
     print(f"mid: free-running token-exact vs reference {n_exact}/{len(cases)}")
@@ -449,11 +379,11 @@ def test_mid_width_batch32_rows_equal_single_rows():
     GEMVs (gate/up, down, o / cross-o, the 65 541-row head) and the 17..32-row GEMM: every
     kernel choice keeps a row's sums independent of the batch, so rows of a 32-row batch
     equal the same utterances run alone and in a batch of 8 (tokens and logits bitwise)."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
-    meta, _ = _load("golden_mid")
+    meta, _ = load_golden("golden_mid")
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     eng = _engine(cfg, sd, max_batch=32, max_text=64, max_audio=128, max_gen=48)
@@ -478,14 +408,14 @@ def test_mid_width_batch32_rows_equal_single_rows():
 
 def test_sampler_kernel_vs_reference_golden():
     """On-device sampler on the reference's sampler golden cases (V = 65541)."""
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     from tests.golden.make_golden import make_sampler_logits
     from t5gemma_tts_amd import _lib
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import reference_noise
     from t5gemma_tts_amd.weights import synthetic_weights
-    meta, _ = _load("golden_sampler")
+    meta, _ = load_golden("golden_sampler")
     cfg = named_config("tiny")
     cfg.audio_vocab_size = 65536
     cfg.empty_token, cfg.eog, cfg.audio_pad_token, cfg.eos, cfg.y_sep_token = 65536, 65537, 65538, 65539, 65540
@@ -549,7 +479,7 @@ def test_generate_without_target_length(max_audio, max_gen):
     also have taken is teacher-forced exact (this path used to raise). The second
     case makes the cache capacity (max_audio - prompt) the cap, so the forced-EOS step samples
     at cur_num_gen == budget: the parity noise buffer holds budget + 1 steps."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import Utterance
     from t5gemma_tts_amd.weights import synthetic_weights
@@ -559,9 +489,9 @@ def test_generate_without_target_length(max_audio, max_gen):
     cap = min(max_gen, max_audio - 3)
     c = {"top_k": 30, "top_p": 0.9, "min_p": 0.0, "temperature": 0.8, "stop_repetition": 3, "silence_tokens": []}
     u = Utterance(x=[5, 17, 301, 44, 9], y=[3, 60, cfg.y_sep_token], tgt_y_len=None)
-    out = eng.generate([u], _params(c), seeds=[11], parity=True, record_logits=True)
+    out = eng.generate([u], golden_params(c), seeds=[11], parity=True, record_logits=True)
     g = out["gen"][0].tolist()
     assert 1 <= len(g) <= cap + 1
     if g[-1] == cfg.eog_inference and len(g) >= cap:   # capacity stop: the last EOS is the engine's
         out = {"gen": [out["gen"][0][:-1]], "logits": out["logits"][:-1]}
-    teacher_forced_check(cfg, sd, u, _oparams(c), 11, out, rtol=0.02)
+    teacher_forced_check(cfg, sd, u, golden_params(c, oracle=True), 11, out, rtol=0.02)

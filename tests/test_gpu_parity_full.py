@@ -24,22 +24,12 @@ import pytest
 import torch
 
 from conftest import GOLDEN, REPO
+from tests.engine_cases import load_golden, need_gpu, topk_agree
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 RTOL = 0.03        # teacher-forced max |gpu - ref| / max |ref| per step (26+26 bf16 layers)
 TOPK = 30
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _load():
-    with open(os.path.join(GOLDEN, "golden_full.json")) as f:
-        meta = json.load(f)
-    return meta, dict(np.load(os.path.join(GOLDEN, "golden_full.npz")))
 
 
 def _long_rows(cfg, n, seed):
@@ -53,17 +43,6 @@ def _long_rows(cfg, n, seed):
     return rows
 
 
-def topk_agree(g, r, k, tol):
-    """Top-k index sets of g and r equal, except members whose value is within ``tol`` of
-    the k-th value (ties at the cut may legitimately swap)."""
-    gv, gi = torch.topk(g.float(), k)
-    rv, ri = torch.topk(r.float(), k)
-    cut = min(gv[-1].item(), rv[-1].item())
-    sg = {int(i) for i, v in zip(gi, gv) if v.item() > cut + tol}
-    sr = {int(i) for i, v in zip(ri, rv) if v.item() > cut + tol}
-    return sg <= set(ri.tolist()) and sr <= set(gi.tolist())
-
-
 def _write(name, payload):
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     with open(os.path.join(REPO, "gpurun_out", name), "w") as f:
@@ -72,14 +51,14 @@ def _write(name, payload):
 
 @pytest.mark.timeout(1200)
 def test_c3_full_depth_batch8_vs_reference():
-    _need_gpu()
+    need_gpu()
     from oracle.t5g_oracle import SamplerParams as OP
     from oracle.t5g_oracle import T5GemmaTTSOracle, draw_noise, sample_helper
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance
     from t5gemma_tts_amd.weights import state_dict_digest, synthetic_weights
 
-    meta, arrs = _load()
+    meta, arrs = load_golden("golden_full")
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     assert state_dict_digest(sd) == meta["weight_sha256"], "weights differ from the golden run"
@@ -196,7 +175,7 @@ def test_c3_full_depth_batch8_vs_reference():
 
 @pytest.mark.timeout(900)
 def test_c3_batch8_exact_vs_reference():
-    _need_gpu()
+    need_gpu()
     import hashlib
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance
@@ -253,7 +232,7 @@ CONFIG_GOLDENS = [("golden_c2", 1, 0), ("golden_c1", 1, 0), ("golden_c4", 8, 3),
 def test_config_golden_exact(name, batch, slot):
     """Parity mode == the reference's own generate on BASELINE rows run to their full
     budget: every token and every step's logits row (sha of the bf16 bits), bitwise."""
-    _need_gpu()
+    need_gpu()
     import hashlib
     import sys
     sys.path.insert(0, REPO)
@@ -308,7 +287,7 @@ def test_sliding_window_long_prompt_golden():
     off: one element of layer 24's prefill attention sat on a bf16 tie that aten broke with
     glibc's expf, not the correctly rounded exp -- tools/dbg/dbg_window_kv.py and
     tools/cpu_order/diag_layer_row.py localised it)"""
-    _need_gpu()
+    need_gpu()
     import hashlib
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance
@@ -351,7 +330,7 @@ def test_fast_path_capacity_is_per_call():
     duration cap) serves a C3 batch of 8 (T_x 60, T_p 151, 751 tokens per row) on the fast
     kernels with tokens identical to an engine of 1 024 keys (the decode grids and the stop
     rule follow the call's key bound, t5g_engine_set_audio_max)."""
-    _need_gpu()
+    need_gpu()
     import bench
     from t5gemma_tts_amd.config import named_config
     from t5gemma_tts_amd.engine import SamplingParams, T5GemmaTTSEngine, Utterance

@@ -36,7 +36,7 @@ def _rms(a, b):
 def _oracle_check(cfg, sd, x, y, tgt, seed, model):
     from oracle.t5g_oracle import SamplerParams
     from t5gemma_tts_amd.engine import SamplingParams, Utterance
-    from tests.test_gpu_parity import teacher_forced_check
+    from tests.engine_cases import teacher_forced_check
     utt = Utterance(x=x, y=y, tgt_y_len=tgt)
     out = model.engine.generate([utt], SamplingParams(top_k=30, top_p=0.9, temperature=0.8, stop_repetition=3),
                                 seeds=[seed], parity=True, record_logits=True)

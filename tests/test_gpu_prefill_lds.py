@@ -9,14 +9,11 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.engine_cases import need_gpu
+
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 PREFILL, PREFILL_REG = 0x100, 0x200
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 @pytest.mark.parametrize("M,N,K,epi", [
@@ -24,7 +21,7 @@ def _need_gpu():
     (12 * 60, 2304, 2048, 0), (16 * 152 - 5, 2304, 2304, 2), (130, 4096, 2304, 0),
 ])
 def test_lds_prefill_equals_register_ring(M, N, K, epi):
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     g = torch.Generator().manual_seed(M + N + K)

@@ -19,12 +19,12 @@ import torch
 
 from oracle.t5g_oracle import apply_rope, inv_freq_table, rope_cos_sin
 from tests import kernel_cases as kc
+from tests.engine_cases import need_gpu
 from tests.kernel_cases import BF16, SENT
 from tests.kernel_cases import bf16_step as _bf16_step
 from tests.kernel_cases import i16 as _i16
 from tests.kernel_cases import sentinel as _sentinel
 from tests.kernel_cases import trig_safe as _trig_safe
-from tests.test_gpu_attention import _need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -172,14 +172,14 @@ ENC_LENS = [11, 1, 25]   # 37 tokens over 3 ragged rows
 def test_encoder_shape(inplace):
     """nq 8, nk 4, nv 4, D 256: 37 tokens over 3 ragged rows in packed (shuffled) order, slots
     from tok_t, a cache larger than every row; q to its own buffer, and in place."""
-    _need_gpu()
+    need_gpu()
     c = Case(1, 8, 4, 4, 256, ENC_LENS, 32, inplace=inplace)
     c.check(*c.run(), label=f"encoder inplace={inplace}")
 
 
 def test_in_place_q_needs_one_stride():
     """Qout == X with ldq != ldx is refused before anything is launched."""
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     x = torch.zeros(4, 4096, dtype=BF16, device="cuda")
     i = torch.zeros(4, dtype=torch.int32, device="cuda")
@@ -196,28 +196,28 @@ def test_in_place_q_needs_one_stride():
 
 def test_cross_kv_shape():
     """The prefill's cross K / V store: no q heads, rope on k only."""
-    _need_gpu()
+    need_gpu()
     c = Case(2, 0, 4, 4, 256, [60, 1, 33], 70, rope_q=0, rope_k=1)
     c.check(*c.run(), label="cross k/v")
 
 
 def test_unrotated_heads_are_copies():
     """rope_q = rope_k = 0: everything is a copy into the right place."""
-    _need_gpu()
+    need_gpu()
     c = Case(3, 8, 4, 4, 256, ENC_LENS, 32, rope_q=0, rope_k=0)
     c.check(*c.run(), label="no rope")
 
 
 def test_tiny_config():
     """D 64 with nq 2, nk 1, nv 1: 128 rotation pairs, half of the one 256-thread block idle."""
-    _need_gpu()
+    need_gpu()
     c = Case(4, 2, 1, 1, 64, [7, 1, 12], 24)
     c.check(*c.run(), label="tiny")
 
 
 def test_column_offset():
     """col0 = 2048: the k | v heads of q | k | v rows, the q heads left alone."""
-    _need_gpu()
+    need_gpu()
     c = Case(5, 0, 4, 4, 256, ENC_LENS, 32, col0=2048)
     c.check(*c.run(), label="col0 2048")
     c = Case(6, 2, 1, 1, 64, [5, 3], 9, col0=40)
@@ -228,7 +228,7 @@ def test_column_offset():
 def test_split_k_slabs(nsplit):
     """X as fp32 split-K slabs: summed in slab order in fp32, rounded to bf16, then rotated. The
     slab values make the sum depend on the order (two large slabs that cancel exactly first)."""
-    _need_gpu()
+    need_gpu()
     c = Case(10 + nsplit, 8, 4, 4, 256, ENC_LENS, 32, nsplit=nsplit)
     if nsplit > 2:
         print(f"nsplit={nsplit}: {c.order_sensitive:.3f} of the bf16 sums differ when the slabs are added in reverse")
@@ -239,7 +239,7 @@ def test_split_k_slabs(nsplit):
 def test_decode_form():
     """tok_row / tok_t null: token m is row m, slot kv_len[m] - 1; cos / sin from the caller's
     table, so no device trig and the whole output is bit-equal."""
-    _need_gpu()
+    need_gpu()
     c = Case(20, 8, 4, 4, 256, [1, 17, 32, 5, 9], 32, decode=True)
     Qb, Kc, Vc = c.run()
     share = c.check(Qb, Kc, Vc, label="decode form")

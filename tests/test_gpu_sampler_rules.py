@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import sampler_cases as SC
+from tests.engine_cases import stream
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -72,10 +73,6 @@ def _launches(cases):
     return out
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _upload_logits(rows_bf16, V, ld):
     d = torch.full((len(rows_bf16), ld), PAD_LOGIT, dtype=BF16)
     for b, r in enumerate(rows_bf16):
@@ -89,18 +86,18 @@ def _setup(eng, cases, V, noise_dev, noise_steps):
     tk, ntk, sl, nsl = SC.shared_lists()
     _lib.check(eng.L.t5g_sampler_setup(eng.h, len(cases), rows, sts, tk, ntk, sl, nsl,
                                        C.c_void_p(noise_dev.data_ptr()) if noise_dev is not None else None,
-                                       noise_steps, _stream()), "setup")
+                                       noise_steps, stream()), "setup")
     return sts
 
 
 def _sample(eng, B, dlg):
     from t5gemma_tts_amd import _lib
-    _lib.check(eng.L.t5g_sample_only(eng.h, B, C.c_void_p(dlg.data_ptr()), dlg.shape[1], _stream()), "sample")
+    _lib.check(eng.L.t5g_sample_only(eng.h, B, C.c_void_p(dlg.data_ptr()), dlg.shape[1], stream()), "sample")
     out = (_lib.SamplerState * B)()
     flags = (C.c_int32 * B)()
-    _lib.check(eng.L.t5g_read_step(eng.h, out, flags, B, _stream()), "read_step")
+    _lib.check(eng.L.t5g_read_step(eng.h, out, flags, B, stream()), "read_step")
     toks = (C.c_int32 * (B * SC.MAX_GEN))()
-    _lib.check(eng.L.t5g_read_tokens(eng.h, toks, B, _stream()), "read_tokens")
+    _lib.check(eng.L.t5g_read_tokens(eng.h, toks, B, stream()), "read_tokens")
     return out, list(flags), [list(toks[b * SC.MAX_GEN:(b + 1) * SC.MAX_GEN]) for b in range(B)]
 
 
@@ -269,7 +266,7 @@ def test_sampler_setup_rejects_out_of_list_rows():
             setattr(rows[1], k, v)
         for k, v in (state_kw or {}).items():
             setattr(sts[1], k, v)
-        return eng.L.t5g_sampler_setup(eng.h, 2, rows, sts, tk, n_tk, sl, n_sl, None, 0, _stream())
+        return eng.L.t5g_sampler_setup(eng.h, 2, rows, sts, tk, n_tk, sl, n_sl, None, 0, stream())
 
     einval = -1
     assert setup(dict(n_silence=3, silence_off=nsl - 2)) == einval          # silence range past the list

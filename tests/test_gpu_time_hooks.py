@@ -1,5 +1,5 @@
 """The hipEvent timing hooks (csrc/engine_hooks.hip; bench.py --full prices its rooflines with
-them) on the golden_mid engine of test_gpu_fused.py (true 2b-2b widths, 2 + 2 layers, max_text
+them) on engine_cases.mid_engine(32), as in test_gpu_fused.py (true 2b-2b widths, 2 + 2 layers, max_text
 64, max_audio 128): after a short generate() the three decode hooks return OK with a finite
 positive time at 3 and at 16 rows, t5g_time_decode_layer refuses 17 rows, a hook leaves the
 decode state marked invalid (t5g_decode then returns T5G_EINVAL), and a fresh generate() with the
@@ -11,7 +11,7 @@ import math
 import pytest
 import torch
 
-from test_gpu_fused import _mid_engine, _need_gpu, _utts
+from tests.engine_cases import default_params, mid_engine, need_gpu, stream, utterances
 
 pytestmark = pytest.mark.gpu
 
@@ -21,26 +21,21 @@ T5G_EINVAL, T5G_EUNSUPPORTED = -1, -3
 
 @pytest.fixture(scope="module")
 def mid():
-    _need_gpu()
-    return _mid_engine(32)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    need_gpu()
+    return mid_engine(32)
 
 
 @pytest.mark.parametrize("B", [3, 16])
 def test_decode_hooks_time_and_leave_generate_unchanged(mid, B):
     from t5gemma_tts_amd import _lib
-    from t5gemma_tts_amd.engine import SamplingParams
     cfg, eng = mid
     L = _lib.lib()
-    utts = _utts(cfg, B, 60 + B)
-    p = SamplingParams(top_k=30, top_p=0.9, temperature=0.8)
+    utts = utterances(cfg, B, 60 + B)
+    p = default_params()
     seeds = list(range(700, 700 + B))
     before = eng.generate(utts, p, seeds=seeds)
     assert sum(len(g) for g in before["gen"]) > B
-    st = _stream()
+    st = stream()
     us, keys = C.c_float(0.0), C.c_float(0.0)
     assert L.t5g_time_decode_step(eng.h, ITERS, st, C.byref(us)) == 0
     assert math.isfinite(us.value) and us.value > 0, us.value
@@ -62,19 +57,19 @@ def test_decode_layer_hook_refuses_17_rows(mid):
     from t5gemma_tts_amd import _lib
     _, eng = mid
     us, keys = C.c_float(0.0), C.c_float(0.0)
-    rc = _lib.lib().t5g_time_decode_layer(eng.h, 17, ITERS, _stream(), C.byref(us), C.byref(keys))
+    rc = _lib.lib().t5g_time_decode_layer(eng.h, 17, ITERS, stream(), C.byref(us), C.byref(keys))
     assert rc == T5G_EUNSUPPORTED
 
 
 def test_time_gemm_and_gemv_smallest_shape():
-    _need_gpu()
+    need_gpu()
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
     M, N, K = 3, 192, 64   # test_gpu_gemv.py CASES: tiny widths, most lanes idle
     g = torch.Generator(device="cpu").manual_seed(9)
     W = (torch.randn(N, K, generator=g) * 0.02).to(torch.bfloat16).cuda()
     X = torch.randn(M, K, generator=g).to(torch.bfloat16).cuda()
-    st = _stream()
+    st = stream()
     Wp = torch.empty(L.t5g_packed_bytes(N, K) // 2, dtype=torch.bfloat16, device="cuda")
     assert L.t5g_pack_weight(C.c_void_p(W.data_ptr()), N, K, K, C.c_void_p(Wp.data_ptr()), st) == 0
     arr = (C.c_void_p * 1)(Wp.data_ptr())

@@ -4,24 +4,18 @@ reference's sampler golden cases. No GPU compute is invoked."""
 import ctypes as C
 import json
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import GOLDEN, REPO
-
-
-def _header_symbols():
-    src = open(os.path.join(REPO, "include", "t5gtts.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(t5g_[a-z_0-9]+)\s*\(", src)))
+from conftest import GOLDEN
+from tests.engine_cases import header_symbols
 
 
 def test_library_exports_header_symbols():
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
-    syms = _header_symbols()
+    syms = header_symbols("t5gtts.h", "t5g")
     assert len(syms) >= 20
     for s in syms:
         assert hasattr(L, s), s

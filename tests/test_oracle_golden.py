@@ -1,6 +1,5 @@
 """Pin the CPU oracle against golden vectors captured from the reference itself
 (tests/golden/make_golden.py). CPU only."""
-import json
 import os
 
 import numpy as np
@@ -8,44 +7,27 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from oracle.t5g_oracle import SamplerParams, T5GemmaTTSOracle, draw_noise, sample_helper, \
+from oracle.t5g_oracle import T5GemmaTTSOracle, draw_noise, sample_helper, \
     top_k_top_p_filtering, RowState
 from t5gemma_tts_amd.config import named_config
 from t5gemma_tts_amd.weights import state_dict_digest, synthetic_weights
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name + ".json")) as f:
-        meta = json.load(f)
-    npz = os.path.join(GOLDEN, name + ".npz")
-    arrs = dict(np.load(npz)) if os.path.exists(npz) else {}
-    return meta, arrs
-
-
-def _params(c):
-    return SamplerParams(top_k=c["top_k"], top_p=c["top_p"], min_p=c["min_p"],
-                         temperature=c["temperature"], stop_repetition=c["stop_repetition"],
-                         silence_tokens=tuple(c["silence_tokens"]))
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).numpy()
+from tests.engine_cases import bf16_bits, golden_params, load_golden
 
 
 @pytest.mark.parametrize("name", ["golden_tiny", "golden_tiny_eager", "golden_tiny_window"])
 def test_oracle_matches_reference_tokens(name):
     if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
         pytest.skip("fixture not generated")
-    meta, arrs = _load(name)
+    meta, arrs = load_golden(name)
     torch.set_num_threads(meta["threads"])
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     assert state_dict_digest(sd) == meta["weight_sha256"], "weight generator drifted"
     orc = T5GemmaTTSOracle(cfg, sd)
     for ci, c in enumerate(meta["cases"]):
-        out = orc.generate(c["x"], c["y"], c["tgt"], _params(c), seed=c["seed"], record_logits=True)
+        out = orc.generate(c["x"], c["y"], c["tgt"], golden_params(c, oracle=True), seed=c["seed"], record_logits=True)
         ref = arrs[f"logits_{ci}"]
-        got = _bits(out["logits"])
+        got = bf16_bits(out["logits"])
         assert got.shape == ref.shape, (ci, got.shape, ref.shape)
         assert np.array_equal(got, ref), f"case {ci}: logits differ at steps {np.nonzero((got != ref).any(1))[0][:5]}"
         assert out["gen"].view(-1).tolist() == c["gen"], ci
@@ -54,7 +36,7 @@ def test_oracle_matches_reference_tokens(name):
 
 def test_sampler_matches_reference():
     from tests.golden.make_golden import make_sampler_logits
-    meta, _ = _load("golden_sampler")
+    meta, _ = load_golden("golden_sampler")
     for c in meta["cases"]:
         logits = make_sampler_logits(c["logit_seed"], c["V"], c["scale"], c["quant"])
         g = torch.Generator().manual_seed(c["noise_seed"])
@@ -77,16 +59,16 @@ def test_oracle_matches_reference_mid():
     name = "golden_mid"
     if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
         pytest.skip("fixture not generated")
-    meta, arrs = _load(name)
+    meta, arrs = load_golden(name)
     torch.set_num_threads(meta["threads"])
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     assert state_dict_digest(sd) == meta["weight_sha256"]
     orc = T5GemmaTTSOracle(cfg, sd)
     for ci, c in enumerate(meta["cases"]):
-        out = orc.generate(c["x"], c["y"], c["tgt"], _params(c), seed=c["seed"], record_logits=True)
+        out = orc.generate(c["x"], c["y"], c["tgt"], golden_params(c, oracle=True), seed=c["seed"], record_logits=True)
         assert out["gen"].view(-1).tolist() == c["gen"], ci
-        bits = _bits(out["logits"])
+        bits = bf16_bits(out["logits"])
         shas = [hashlib.sha256(r.astype(np.int16).tobytes()).hexdigest()[:16] for r in bits]
         assert shas == c["logit_sha"], ci
 
@@ -99,16 +81,16 @@ def test_oracle_matches_reference_full_depth():
     name = "golden_full"
     if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
         pytest.skip("fixture not generated")
-    meta, arrs = _load(name)
+    meta, arrs = load_golden(name)
     torch.set_num_threads(meta["threads"])
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     assert state_dict_digest(sd) == meta["weight_sha256"]
     orc = T5GemmaTTSOracle(cfg, sd)
     for ci, c in enumerate(meta["cases"]):
-        out = orc.generate(c["x"], c["y"], c["tgt"], _params(c), seed=c["seed"], record_logits=True)
+        out = orc.generate(c["x"], c["y"], c["tgt"], golden_params(c, oracle=True), seed=c["seed"], record_logits=True)
         assert out["gen"].view(-1).tolist() == c["gen"], ci
-        bits = _bits(out["logits"])
+        bits = bf16_bits(out["logits"])
         shas = [hashlib.sha256(r.astype(np.int16).tobytes()).hexdigest()[:16] for r in bits]
         assert shas == c["logit_sha"], ci
         top = torch.topk(out["logits"].float(), 64, dim=-1)
@@ -119,7 +101,7 @@ def test_oracle_fp64_restatement_tracks_bf16():
     """The fp64 restatement (noise-floor yardstick of test_gpu_noise_floor.py) runs the same
     graph: on the tiny golden case its logits stay within bf16 rounding noise of the bf16
     oracle's, and the bf16 oracle itself is unchanged (pinned by the goldens above)."""
-    meta, _ = _load("golden_tiny")
+    meta, _ = load_golden("golden_tiny")
     cfg = named_config(meta["config"], **meta["config_kw"])
     sd = synthetic_weights(cfg, meta["weight_seed"])
     c = meta["cases"][0]

@@ -5,7 +5,6 @@ transcription."""
 import ctypes as C
 import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,6 +14,7 @@ import torch
 import t5gemma_tts_amd  # noqa: F401
 from t5gemma_tts_amd import whisper_asr as w
 from conftest import GOLDEN, REPO
+from tests.engine_cases import header_symbols
 
 sys.path.insert(0, os.path.join(REPO, "oracle"))
 sys.path.insert(0, GOLDEN)
@@ -183,16 +183,10 @@ def test_suppress_lists(tmp_path):
     assert not torch.isinf(logits).any()
 
 
-def _header_symbols():
-    src = open(os.path.join(REPO, "include", "whisper.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(whs_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_whs_exports_and_struct_sizes():
     from t5gemma_tts_amd import _lib
     L = _lib.lib()
-    syms = _header_symbols()
+    syms = header_symbols("whisper.h", "whs")
     assert set(syms) == set(w.WHS_SIGNATURES), set(syms) ^ set(w.WHS_SIGNATURES)
     for s in syms:
         assert hasattr(L, s), s

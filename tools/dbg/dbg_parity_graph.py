@@ -9,7 +9,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import t5gemma_tts_amd  # noqa: E402,F401
-from test_gpu_parity import _engine, _load, _oparams, _params  # noqa: E402
+from test_gpu_parity import _engine  # noqa: E402
+from tests.engine_cases import golden_params as _params  # noqa: E402
+from tests.engine_cases import load_golden as _load  # noqa: E402
 from t5gemma_tts_amd.config import named_config  # noqa: E402
 from t5gemma_tts_amd.engine import Utterance  # noqa: E402
 from t5gemma_tts_amd.weights import synthetic_weights  # noqa: E402

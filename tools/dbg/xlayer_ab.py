@@ -7,7 +7,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import torch  # noqa: E402
-from test_gpu_xlayer import _mid_engine, _utts  # noqa: E402
+from tests.engine_cases import mid_engine as _mid_engine  # noqa: E402
+from tests.engine_cases import utterances as _utts  # noqa: E402
 
 
 def main():

@@ -12,7 +12,8 @@ import torch  # noqa: E402
 
 
 def main():
-    from test_gpu_fused import _mid_engine, _utts
+    from tests.engine_cases import mid_engine as _mid_engine
+    from tests.engine_cases import utterances as _utts
     from t5gemma_tts_amd.engine import SamplingParams
     R = int(sys.argv[1]) if len(sys.argv) > 1 else 6
     Bs = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [16, 12]
