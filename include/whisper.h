@@ -93,6 +93,22 @@ int whs_encode(whs_model* m, int32_t seek, int32_t seg_frames, float* feat_out, 
  * whs_encode; logits [n][n_vocab]. offset 0 starts a new sequence (cache reset). */
 int whs_decode(whs_model* m, const int32_t* tokens, int32_t n, int32_t offset, float* logits, void* stream);
 
+/* Diagnostics: single ops of the text decoder on caller buffers (device, fp32), through the
+ * dispatch whs_decode itself uses. Each returns -1 before any launch for a bad argument.
+ *
+ * Attention of Tq queries Q [Tq][64 * heads] over Tk keys / values with row stride ldkv
+ * (ldkv % 4 == 0, ldkv >= 64 * heads; heads = the model's n_text_head) into O [Tq][64 * heads].
+ * causal: query i sees keys [0, q_off + i], and q_off + Tq <= Tk. Tq == 1 takes the split +
+ * merge kernels (all Tk keys, so a causal call needs q_off + 1 == Tk; Tk <= max(n_audio_ctx,
+ * n_text_ctx), the model's split workspace); Tq > 1 the tiled kernel. */
+int whs_attention_op(whs_model* m, const float* Q, const float* K, const float* V, int32_t ldkv, int32_t Tq,
+                     int32_t Tk, int32_t causal, int32_t q_off, float* O, void* stream);
+/* Y [M][N] = epi(X [M][K] . W [N][K]^T + bias [N]) + resid [M][N] (bias, resid optional; epi 0
+ * none, 4 exact GELU): the GEMV for M <= 4 and K % 4 == 0, else the tiled GEMM, which needs
+ * K % 32 == 0 (-1 otherwise). */
+int whs_linear_op(const float* X, int32_t M, const float* W, int32_t N, int32_t K, const float* bias,
+                  const float* resid, int32_t epi, float* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

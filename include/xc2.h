@@ -161,20 +161,20 @@ typedef struct xc2e_conv {        /* Conv1d / Linear: weights tap-major [cout][k
     int32_t cin, cout, k, stride, dil, pad, kpad;
 } xc2e_conv;
 
-typedef struct xc2e_snake {       /* SnakeBeta log-parameters [C] (the kernel takes exp) */
-    const float *alpha, *beta;
-} xc2e_snake;
+typedef struct xc2e_snake_par {   /* SnakeBeta log-parameters [C] (the kernel takes exp); */
+    const float *alpha, *beta;    /* xc2e_snake is the activation's single-op entry point */
+} xc2e_snake_par;
 
 typedef struct xc2e_resunit {     /* [tf] Xcodec2ResidualUnit :548-581 */
-    xc2e_snake s1;
+    xc2e_snake_par s1;
     xc2e_conv c1;                 /* k7, dilation 1 / 3 / 9 */
-    xc2e_snake s2;
+    xc2e_snake_par s2;
     xc2e_conv c2;                 /* k1 */
 } xc2e_resunit;
 
 typedef struct xc2e_block {       /* [tf] Xcodec2EncoderBlock :584-604 */
     xc2e_resunit ru[3];
-    xc2e_snake s;
+    xc2e_snake_par s;
     xc2e_conv down;               /* k = 2 * stride, pad = ceil(stride / 2) */
 } xc2e_block;
 
@@ -202,7 +202,7 @@ typedef struct xc2e_weights {
     xc2e_conv adapter[4];         /* [tf] Xcodec2SemanticAdapter :865-909 (k3, pad 1) */
     xc2e_conv ac_in;              /* Conv1d(1 -> c0, k7, pad 3) */
     xc2e_block blocks[XC2E_MAX_BLOCKS];
-    xc2e_snake ac_snake;
+    xc2e_snake_par ac_snake;
     xc2e_conv ac_out;             /* Conv1d(c0 * 2^n_blocks -> hidden, k3, pad 1) */
     const float *fc_w, *fc_b;     /* [sem_hidden + hidden] square */
     const float *pin_w, *pin_b;   /* project_in [n_levels][sem_hidden + hidden] */
@@ -224,6 +224,27 @@ int xc2e_encode(xc2_encoder* e, const float* wav_dev, int32_t n_samples, int32_t
 /* Diagnostics: the semantic model's input features alone (fbank front end), fp32
  * [num_codes][160] into feat_dev. */
 int xc2e_features(xc2_encoder* e, const float* wav_dev, int32_t n_samples, float* feat_dev, void* stream);
+
+/* Diagnostics: single ops of the encoder on caller buffers (device, fp32), through the launch
+ * helpers xc2e_encode itself uses; no encoder handle. Each returns -1 before any launch for a
+ * null pointer, T <= 0 or the limits named below.
+ *
+ * Relative-key self attention ([tf] Wav2Vec2BertSelfAttention, head size 64): qkv
+ * [T][3 * 64 * heads] (q | k | v), qe [T][heads][L + R + 1] = q . distance_embedding,
+ * out [T][64 * heads]. heads >= 1, L >= 0, R >= 0. */
+int xc2e_attention_relkey(const float* qkv, int32_t T, int32_t heads, const float* qe, int32_t L, int32_t R,
+                          float* out, void* stream);
+/* Anti-aliased SnakeBeta ([tf] Xcodec2AntiAliasedActivation1d) over x [T][C] -> y [T][C];
+ * alpha_log / beta_log [C], up12 / down12 the 12-tap filters. form 0: the encoder's own
+ * dispatch (4 outputs per thread where T % 4 == 0 and T >= 8); form 1: the per-output kernel
+ * at every T. C >= 1, T * C <= 2^31. */
+int xc2e_snake(const float* x, int32_t T, int32_t C, const float* alpha_log, const float* beta_log,
+               const float* up12, const float* down12, float* y, int32_t form, void* stream);
+/* Conformer convolution module between its pointwise convs ([tf] Wav2Vec2BertConvolutionModule):
+ * p1 [T][2H] -> GLU -> causal depthwise conv dw [H][KW] -> LayerNorm(ln_w, ln_b, eps) -> swish
+ * -> out [T][H]. H % 4 == 0, H <= 1024, KW >= 1. */
+int xc2e_conv_module_mid(const float* p1, int32_t T, int32_t H, int32_t KW, const float* dw, const float* ln_w,
+                         const float* ln_b, float eps, float* out, void* stream);
 
 #ifdef __cplusplus
 }

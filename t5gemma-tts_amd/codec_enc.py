@@ -265,6 +265,13 @@ XC2E_SIGNATURES = {
     "xc2e_num_codes": (C.c_int32, [C.c_void_p, C.c_int32]),
     "xc2e_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "xc2e_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    # single-op diagnostics (tests/test_gpu_codec_enc_ops.py)
+    "xc2e_attention_relkey": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p]),
+    "xc2e_snake": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_int32, C.c_void_p]),
+    "xc2e_conv_module_mid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -658,4 +658,31 @@ int whs_decode(whs_model* m, const int32_t* tokens, int32_t n, int32_t offset, f
     return dgemm(wg(m->dxn, C, w.tok_emb, C, k.n_vocab, nullptr, logits, k.n_vocab, n), st);
 }
 
+// ---- single-op diagnostics: the decoder's dispatch helpers on caller buffers
+int whs_attention_op(whs_model* m, const float* Q, const float* K, const float* V, int32_t ldkv, int32_t Tq,
+                     int32_t Tk, int32_t causal, int32_t q_off, float* O, void* stream) {
+    if (!m || !Q || !K || !V || !O || Tq <= 0 || Tk <= 0 || q_off < 0 || causal < 0 || causal > 1 || ldkv <= 0 ||
+        ldkv % 4)
+        return -1;
+    const whs_config& k = m->cfg;
+    const int heads = k.n_text_head;
+    if (ldkv < 64 * heads) return -1;
+    if (causal && (long)q_off + Tq > Tk) return -1;
+    if (Tq == 1) {
+        // the split partials live in the model's workspace; the split kernel sees every key
+        if (Tk > (k.n_audio_ctx > k.n_text_ctx ? k.n_audio_ctx : k.n_text_ctx)) return -1;
+        if (causal && q_off + 1 != Tk) return -1;
+    }
+    return dec_attention(m, Q, K, V, ldkv, O, Tq, Tk, heads, causal, q_off, (hipStream_t)stream);
+}
+
+int whs_linear_op(const float* X, int32_t M, const float* W, int32_t N, int32_t K, const float* bias,
+                  const float* resid, int32_t epi, float* Y, void* stream) {
+    if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0 || (epi != EPI_NONE && epi != EPI_GELU)) return -1;
+    GemmArgs g = wg(X, K, W, K, N, bias, Y, N, M);
+    g.resid = resid;
+    g.epi = epi;
+    return dgemm(g, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -61,11 +61,16 @@ struct GemmArgs {
 };
 
 constexpr int BM = 128, BN = 128, BK = 32, LDT = BK + 4;
+// The MFMA chain of one output is a sequential fp32 sum, whose rounding error grows like
+// sqrt(K) (6.7e-6 on unit-variance outputs at K = 5120, ten times a GEMV's tree sum). So the
+// chain runs over KSUM k-tiles (256 k) at a time and the partial sums are added into a second
+// accumulator; K <= 256 is one partial sum, bit for bit the plain chain.
+constexpr int KSUM = 8;
 
 // 256 threads = 4 waves in 2x2; each wave owns a 64x64 tile = 2x2 MFMA 32x32 tiles.
 // K is consumed in groups of 8: lane half h takes k = 8g + 4h + e in MFMA step e, so
 // every operand fetch is one 16-byte LDS read per 4 MFMAs.
-__global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
+__global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs a) {   // two blocks a CU: what the LDS allows
     __shared__ float As[2][BM * LDT];
     __shared__ float Ws[2][BN * LDT];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -90,13 +95,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
     }
     const bool am_ok = m0 + BM <= a.M, wn_ok = n0 + BN <= a.N;
     f32x4 ra[4], rw[4];
-    f32x16 acc[2][2];
+    f32x16 acc[2][2], tot[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.f;
 
     const int nk = a.K / BK;
 #pragma unroll
@@ -140,6 +145,16 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
                     for (int j = 0; j < 2; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
         }
+        if ((kt & (KSUM - 1)) == KSUM - 1 || kt == nk - 1) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    tot[i][j] += acc[i][j];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                }
+        }
     }
     // epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                float v = acc[i][j][r] + bn;
+                float v = tot[i][j][r] + bn;
                 if (m >= a.M || n >= a.N) continue;
                 if (a.epi == EPI_SILU) v = silu(v);
                 else if (a.epi == EPI_RELU) v = fmaxf(v, 0.f);

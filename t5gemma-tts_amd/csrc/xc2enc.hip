@@ -454,17 +454,44 @@ static int conv(xc2_encoder* e, const xc2e_conv& c, const float* X, int T_in, fl
     return gemm(g, st);
 }
 
-static int snake(const float* X, float* Y, int T, int C, const xc2e_snake& s, const xc2e_weights& w, hipStream_t st) {
-    if (T % 4 == 0 && T >= 8) {
+// form 0: the encoder's dispatch (4 outputs per thread where T allows); form 1: the per-output
+// kernel at every T (xc2e_snake compares the two)
+static int snake_launch(const float* X, float* Y, int T, int C, const float* alpha_log, const float* beta_log,
+                        const float* fu, const float* fd, int form, hipStream_t st) {
+    if (form == 0 && T % 4 == 0 && T >= 8) {
         const long n = (long)(T / 4) * C;
         hipLaunchKernelGGL(aa_snake4_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, X, Y, T, C,
-                           s.alpha, s.beta, w.aa_up, w.aa_down);
+                           alpha_log, beta_log, fu, fd);
         XE_LAUNCHED();
         return 0;
     }
     const long n = (long)T * C;
-    hipLaunchKernelGGL(aa_snake_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, X, Y, T, C, s.alpha,
-                       s.beta, w.aa_up, w.aa_down);
+    hipLaunchKernelGGL(aa_snake_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, X, Y, T, C, alpha_log,
+                       beta_log, fu, fd);
+    XE_LAUNCHED();
+    return 0;
+}
+
+static int snake(const float* X, float* Y, int T, int C, const xc2e_snake_par& s, const xc2e_weights& w, hipStream_t st) {
+    return snake_launch(X, Y, T, C, s.alpha, s.beta, w.aa_up, w.aa_down, 0, st);
+}
+
+// relative-key attention over the fused [T][3 * 64 * heads] projection buffer
+static int attention_relkey(const float* qkv, int T, int heads, const float* qe, int L, int R, float* out,
+                            hipStream_t st) {
+    const int H = 64 * heads;
+    hipLaunchKernelGGL(attn_relkey_kernel, dim3((T + AQ - 1) / AQ, heads), dim3(256), 0, st, qkv, 3 * H, H, heads, out,
+                       T, 0.125f, qe, L, R);
+    XE_LAUNCHED();
+    return 0;
+}
+
+// GLU -> causal depthwise conv -> LayerNorm -> swish between the module's two pointwise convs
+static int conv_module_mid(const float* p1, int T, int H, int KW, const float* dw, const float* lw, const float* lb,
+                           float eps, float* out, hipStream_t st) {
+    // whole waves (a partial wave's cross-lane sums would read inactive lanes)
+    hipLaunchKernelGGL(glu_dwconv_ln_swish_kernel, dim3(T), dim3(((H / 4 + 63) / 64) * 64), 0, st, p1, H, KW, dw, lw,
+                       lb, eps, out);
     XE_LAUNCHED();
     return 0;
 }
@@ -621,9 +648,7 @@ static int semantic(xc2_encoder* e, const float* wav, int n, int T, hipStream_t 
             g.am = RowMap{k.sem_heads, 3 * H / 64, 0};
             XE_TRY(gemm(g, st));
         }
-        hipLaunchKernelGGL(attn_relkey_kernel, dim3((T + AQ - 1) / AQ, k.sem_heads), dim3(256), 0, st, e->qkv, 3 * H,
-                           H, k.sem_heads, e->att, T, 0.125f, e->qe, k.rel_left, k.rel_right);
-        XE_LAUNCHED();
+        XE_TRY(attention_relkey(e->qkv, T, k.sem_heads, e->qe, k.rel_left, k.rel_right, e->att, st));
         {
             GemmArgs g = eg(e->att, H, L.o_w, H, H, L.o_b, e->x, H, T);
             g.resid = e->x;
@@ -632,9 +657,7 @@ static int semantic(xc2_encoder* e, const float* wav, int n, int T, hipStream_t 
         // convolution module
         XE_TRY(layer_norm(e->x, e->xn, T, H, L.conv_ln_w, L.conv_ln_b, eps, st));
         XE_TRY(gemm(eg(e->xn, H, L.pw1_w, H, 2 * H, nullptr, e->p1, 2 * H, T), st));
-        hipLaunchKernelGGL(glu_dwconv_ln_swish_kernel, dim3(T), dim3(((H / 4 + 63) / 64) * 64), 0, st, e->p1, H, k.dw_kernel, L.dw_w,
-                           L.dw_ln_w, L.dw_ln_b, eps, e->dwo);
-        XE_LAUNCHED();
+        XE_TRY(conv_module_mid(e->p1, T, H, k.dw_kernel, L.dw_w, L.dw_ln_w, L.dw_ln_b, eps, e->dwo, st));
         {
             GemmArgs g = eg(e->dwo, H, L.pw2_w, H, H, nullptr, e->x, H, T);
             g.resid = e->x;
@@ -719,6 +742,26 @@ int xc2e_features(xc2_encoder* e, const float* wav, int32_t n, float* feat, void
     XE_TRY(fbank(e, wav, n, T, st));
     return hipMemcpyAsync(feat, e->lm, (size_t)T * 2 * FB_MELS * sizeof(float), hipMemcpyDeviceToDevice, st) ==
                    hipSuccess ? 0 : -2;
+}
+
+// ---- single-op diagnostics: the launch helpers of semantic() / acoustic() on caller buffers
+int xc2e_attention_relkey(const float* qkv, int32_t T, int32_t heads, const float* qe, int32_t L, int32_t R, float* out,
+                          void* stream) {
+    if (!qkv || !qe || !out || T <= 0 || heads <= 0 || heads > 1024 || L < 0 || R < 0) return -1;
+    return attention_relkey(qkv, T, heads, qe, L, R, out, (hipStream_t)stream);
+}
+
+int xc2e_snake(const float* x, int32_t T, int32_t C, const float* alpha_log, const float* beta_log, const float* up12,
+               const float* down12, float* y, int32_t form, void* stream) {
+    if (!x || !alpha_log || !beta_log || !up12 || !down12 || !y || T <= 0 || C <= 0 || form < 0 || form > 1) return -1;
+    if ((long)T * C > (1L << 31)) return -1;   // one thread per output: the grid's block count
+    return snake_launch(x, y, T, C, alpha_log, beta_log, up12, down12, form, (hipStream_t)stream);
+}
+
+int xc2e_conv_module_mid(const float* p1, int32_t T, int32_t H, int32_t KW, const float* dw, const float* ln_w,
+                         const float* ln_b, float eps, float* out, void* stream) {
+    if (!p1 || !dw || !ln_w || !ln_b || !out || T <= 0 || H <= 0 || H % 4 || H > 1024 || KW < 1) return -1;
+    return conv_module_mid(p1, T, H, KW, dw, ln_w, ln_b, eps, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

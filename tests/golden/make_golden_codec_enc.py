@@ -10,6 +10,11 @@ the hop-padded waveform with 160 zeros either side (the port's own extractor nee
 torchaudio, absent here) -- and records ``Xcodec2Model.encode``'s codes plus the
 project_in latents, for a seeded speech-like waveform of a length that is not a
 multiple of the hop.
+
+``python tests/golden/make_golden_codec_enc.py NAME ...`` writes only the named goldens. The
+ones in LONG are at prompt lengths (tests/test_golden_coverage_cpu.py pins what each is for)
+and hold results only: the waveform is rebuilt from ``wave_seed`` by the test, and the
+features are kept at every ``feature_row_stride``-th frame so a file stays under 200 KB.
 """
 from __future__ import annotations
 
@@ -66,7 +71,8 @@ def features(wav: torch.Tensor) -> torch.Tensor:
     return fe(F.pad(x, (160, 160)).numpy(), sampling_rate=16000, return_tensors="pt")["input_features"]
 
 
-def run(name: str, cfg: EncoderConfig, seed: int, n: int, wave_seed: int):
+def run(name: str, cfg: EncoderConfig, seed: int, n: int, wave_seed: int, results_only: bool = False,
+        feature_row_stride: int = 1):
     from transformers import Xcodec2Model
     torch.manual_seed(0)
     model = Xcodec2Model(hf_config(cfg)).eval()
@@ -94,21 +100,47 @@ def run(name: str, cfg: EncoderConfig, seed: int, n: int, wave_seed: int):
     b = (p + shift).tanh() * half_range - offset
     b = (b + shift).tanh() * half_range - offset
     margin = (b - torch.floor(b) - 0.5).abs().min().item()
-    np.savez_compressed(os.path.join(HERE, f"golden_codec_enc_{name}.npz"), wav=wav.numpy(),
-                        features=feat[0].numpy().astype(np.float32), codes=codes.numpy(),
-                        latent=p.numpy().astype(np.float32))
+    arrays = dict(features=feat[0, ::feature_row_stride].numpy().astype(np.float32), codes=codes.numpy(),
+                  latent=p.numpy().astype(np.float32))
+    if not results_only:
+        arrays["wav"] = wav.numpy()
+    np.savez_compressed(os.path.join(HERE, f"golden_codec_enc_{name}.npz"), **arrays)
+    # frames a fp32 reordering may flip: a bounded latent within 2e-3 of a rounding boundary
+    near = int(((b - torch.floor(b) - 0.5).abs() < 2e-3).any(dim=1).sum())
     meta = {"source": "tests/golden/make_golden_codec_enc.py (transformers Xcodec2Model.encode + "
                       "SeamlessM4TFeatureExtractor)", "config": cfg.__dict__ | {"strides": list(cfg.strides),
                                                                                  "levels": list(cfg.levels)},
             "weight_seed": seed, "n_samples": n, "wave_seed": wave_seed, "n_codes": int(codes.numel()),
             "distinct_codes": int(codes.unique().numel()), "min_rounding_margin": margin,
             "torch_threads": torch.get_num_threads()}
+    if results_only:
+        meta |= {"feature_row_stride": feature_row_stride, "frames_near_boundary": near}
     with open(os.path.join(HERE, f"golden_codec_enc_{name}.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print(name, meta)
 
 
+RUNS = {
+    "tiny": lambda: run("tiny", encoder_tiny(), seed=31, n=13_337, wave_seed=5),
+    "full16k": lambda: run("full16k", encoder_16k(), seed=32, n=20_111, wave_seed=6),
+}
+# name -> (config, weight seed, samples, wave seed, feature row stride)
+LONG = {
+    # 334 frames: three query blocks, six key tiles, distances past rel_left = 64
+    "tiny_long": (encoder_tiny, 31, 106_789, 7, 2),
+    # 200 frames: all six snake lengths (64000 .. 1000, 200) are multiples of 4
+    "tiny_t200": (encoder_tiny, 31, 63_777, 8, 1),
+    # 3 frames: the shortest useful prompt
+    "tiny_short": (encoder_tiny, 31, 700, 9, 1),
+    # 134 frames at the real widths: a second query block, a third key tile
+    "full16k_mid": (encoder_16k, 32, 42_777, 10, 1),
+}
+for _name, (_cfg, _seed, _n, _ws, _stride) in LONG.items():
+    RUNS[_name] = (lambda a=_name, c=_cfg, s=_seed, n=_n, w=_ws, f=_stride:
+                   run(a, c(), seed=s, n=n, wave_seed=w, results_only=True, feature_row_stride=f))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    run("tiny", encoder_tiny(), seed=31, n=13_337, wave_seed=5)
-    run("full16k", encoder_16k(), seed=32, n=20_111, wave_seed=6)
+    for name in (sys.argv[1:] or list(RUNS)):
+        RUNS[name]()

@@ -7,7 +7,9 @@ rescale moves the windowed block cases as far, that the slab values tell a slab 
 the share of RoPE pairs next to a bf16 tie is what the safe-set rule expects. Also the decode
 attention call and its fp64 reference (tests/test_gpu_attention.py, test_gpu_attn_chunk_scores.py)
 and the order-revealing bf16 generator of the exact-order tests; tests/test_engine_cases_cpu.py
-pins what they draw.
+pins what they draw. Last, the fp32 single-op kernels of the codec encoder and the Whisper decoder
+(tests/test_gpu_codec_enc_ops.py, test_gpu_whisper_ops.py): the module formulas that serve as
+fp64 reference and as fp32 yardstick, the bound built from the two, and the peaked-score inputs.
 """
 import functools
 
@@ -310,3 +312,135 @@ def blocks_window_case(window):
     shift = (wrong - exact[0].view(4, 2, 256)[:, 0]).abs().max().item()
     assert (m2 > m1 + 0.5).all() and shift >= 10 * bound, (window, m1.tolist(), m2.tolist(), shift, bound)
     return qi, exact, bound, shift
+
+
+# ---------------------------------------------------------------------------
+# fp32 single-op kernels of the codec encoder and the Whisper decoder against fp64
+# (tests/test_gpu_codec_enc_ops.py, tests/test_gpu_whisper_ops.py): each formula below is the
+# transformers / openai-whisper module the kernel cites, in plain torch at the dtype of its
+# inputs, so one definition gives the fp64 reference and the fp32 evaluation that sets the bound.
+FP32_FACTOR = 8   # a different summation order and the device expf / sinf / erff
+
+
+def _cast(x, dt):
+    return x.to(dt) if torch.is_tensor(x) and x.is_floating_point() else x
+
+
+def fp64_and_fp32(formula, *args, **kw):
+    """(the formula in fp64, max |the formula in fp32 on the CPU - that|), from the same fp32 inputs."""
+    ref = formula(*[_cast(a, torch.float64) for a in args], **kw)
+    lo = formula(*[_cast(a, torch.float32) for a in args], **kw)
+    assert ref.dtype == torch.float64 and lo.dtype == torch.float32
+    return ref, (lo.double() - ref).abs().max().item()
+
+
+def fp32_op_error(tag, got, ref, err32):
+    """The kernel's max error against fp64, printed beside the fp32 evaluation's own and the bound
+    FP32_FACTOR x that one (which never looks at the kernel's output)."""
+    got = got.detach().cpu().double()
+    assert got.shape == ref.shape, (tag, got.shape, ref.shape)
+    assert bool(torch.isfinite(got).all()), tag
+    err = (got - ref).abs().max().item()
+    print(f"{tag}: kernel vs fp64 {err:.3e}, fp32 torch vs fp64 {err32:.3e}, bound {FP32_FACTOR * err32:.3e}")
+    return err
+
+
+def check_fp32_op(tag, got, ref, err32):
+    """fp32_op_error, asserted: at most FP32_FACTOR x the fp32 evaluation's own error."""
+    err = fp32_op_error(tag, got, ref, err32)
+    assert err <= FP32_FACTOR * err32, (tag, err, err32)
+    return err
+
+
+def relkey_attention(qkv, qe, heads, L, R, shift=0):
+    """[tf] Wav2Vec2BertSelfAttention.forward, position_embeddings_type "relative_key", from the
+    projections: qkv [T][3 * 64 * heads] (q | k | v), qe [T][heads][L + R + 1] = q . distance
+    embedding. shift: added to the distance index (a reference-only tooth: what a wrong index
+    would compute)."""
+    T, H = qkv.shape[0], 64 * heads
+    q, k, v = (qkv[:, i * H:(i + 1) * H].reshape(T, heads, 64).transpose(0, 1) for i in range(3))
+    scores = torch.matmul(q, k.transpose(-2, -1)) / 8.0
+    distance = torch.arange(T).view(1, -1) - torch.arange(T).view(-1, 1)
+    idx = (torch.clamp(distance, -L, R) + L + shift).clamp(0, L + R)
+    rel = qe.transpose(0, 1).gather(2, idx[None].expand(heads, T, T))
+    scores = scores + rel / 8.0
+    out = torch.matmul(torch.softmax(scores, dim=-1), v)
+    return out.transpose(0, 1).reshape(T, H)
+
+
+def relkey_scores(qkv, qe, heads, L, R):
+    """The fp64 scores [heads][T][T] of relkey_attention (for the marker margins)."""
+    T, H = qkv.shape[0], 64 * heads
+    q, k = (qkv[:, i * H:(i + 1) * H].double().reshape(T, heads, 64).transpose(0, 1) for i in range(2))
+    distance = torch.arange(T).view(1, -1) - torch.arange(T).view(-1, 1)
+    idx = torch.clamp(distance, -L, R) + L
+    return (torch.matmul(q, k.transpose(-2, -1)) + qe.double().transpose(0, 1).gather(2, idx[None].expand(heads, T, T))) / 8.0
+
+
+def aa_snake(x, alpha_log, beta_log, filt):
+    """[tf] Xcodec2AntiAliasedActivation1d(Xcodec2SnakeBeta): UpSample1d(2, 12) -> SnakeBeta ->
+    DownSample1d(2, 12), on x [T][C] time-major."""
+    import torch.nn.functional as F
+    h = x.t()[None]
+    C = h.shape[1]
+    f = filt.view(1, 1, 12).expand(C, -1, -1)
+    h = F.pad(h, (5, 5), mode="replicate")
+    h = 2 * F.conv_transpose1d(h, f, stride=2, groups=C)
+    h = h[..., 15:-15]
+    alpha = torch.exp(alpha_log)[None, :, None]
+    beta = torch.exp(beta_log)[None, :, None]
+    h = h + (1.0 / (beta + 0.000000001)) * torch.pow(torch.sin(h * alpha), 2)
+    h = F.pad(h, (5, 6), mode="replicate")
+    h = F.conv1d(h, f, stride=2, groups=C)
+    return h[0].t().contiguous()
+
+
+def conv_module_mid(p1, dw, ln_w, ln_b, eps):
+    """[tf] Wav2Vec2BertConvolutionModule.forward between pointwise_conv1 and pointwise_conv2:
+    GLU, left pad KW - 1, depthwise conv, LayerNorm, swish. p1 [T][2H], dw [H][KW] -> [T][H]."""
+    import torch.nn.functional as F
+    H, KW = dw.shape
+    h = F.glu(p1.t()[None], dim=1)
+    h = F.pad(h, (KW - 1, 0))
+    h = F.conv1d(h, dw[:, None, :], groups=H)
+    h = F.layer_norm(h.transpose(1, 2), (H,), ln_w, ln_b, eps)
+    return F.silu(h)[0].contiguous()
+
+
+def whisper_attention(Q, K, V, heads, causal, q_off, past=0):
+    """whisper/model.py MultiHeadAttention.qkv_attention (head size 64: softmax(q k^T / 8) v);
+    causal: query i sees keys [0, q_off + i + past] (past = 1: the reference-only tooth, a mask one
+    key late). Q [Tq][64 * heads]; K, V [Tk][>= 64 * heads]."""
+    Tq, Tk, H = Q.shape[0], K.shape[0], 64 * heads
+    q = Q.reshape(Tq, heads, 64).transpose(0, 1)
+    k = K[:, :H].reshape(Tk, heads, 64).transpose(0, 1)
+    v = V[:, :H].reshape(Tk, heads, 64).transpose(0, 1)
+    s = torch.matmul(q, k.transpose(-2, -1)) * 0.125
+    if causal:
+        hidden = torch.arange(Tk).view(1, -1) > torch.arange(Tq).view(-1, 1) + q_off + past
+        s = s.masked_fill(hidden[None], float("-inf"))
+    return torch.matmul(torch.softmax(s, dim=-1), v).transpose(0, 1).reshape(Tq, H)
+
+
+def whisper_linear(X, W, bias, resid, gelu):
+    """nn.Linear, then the exact (erf) nn.GELU of the MLP, then the block's residual add."""
+    import torch.nn.functional as F
+    y = F.linear(X, W, bias)
+    if gelu:
+        y = F.gelu(y)
+    return y if resid is None else y + resid
+
+
+def peaked_qkv(g, Tq, Tk, heads, marker, gain=9.0):
+    """q [Tq][heads][64], k, v [Tk][heads][64]: every query is 20 u + noise for one unit direction
+    u per head, so ordinary scores (q . k / 8) spread over about +-8 (sigma 2.7), and key
+    `marker` is gain x u -- a score of gain / 8 x (20 +- 4) for every query, 8 or more above every
+    other key's -- with V = +4: the running maximum moves when the marker's tile comes."""
+    u = torch.randn(heads, 64, generator=g)
+    u = u / u.norm(dim=-1, keepdim=True)
+    q = torch.randn(Tq, heads, 64, generator=g) + 20.0 * u
+    k = torch.randn(Tk, heads, 64, generator=g)
+    v = torch.randn(Tk, heads, 64, generator=g)
+    k[marker] = gain * u
+    v[marker] = 4.0
+    return q.contiguous(), k.contiguous(), v.contiguous(), u

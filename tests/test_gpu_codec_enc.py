@@ -9,9 +9,20 @@ and at the real 16 kHz dims (w2v-BERT 16 x 1024, acoustic 48 -> 1536 channels):
 * the codec ids equal, except where the golden latent sits within 2e-3 of an FSQ rounding
   boundary (a tie the fp32 order could flip; measured on MI355X: every id equal, 42/42
   and 63/63, features within 1.3e-5, latents within 1.5e-5 x RMS).
+The goldens named in LONG are at prompt lengths (134 .. 334 frames, and the shortest, 3): a
+second and third 128-query block and up to six 64-key tiles of attn_relkey_kernel, distances
+past rel_left = 64, the conv module's steady state, and -- at 200 frames -- the 4-wide snake
+kernel at all six acoustic lengths. They hold results only; the waveform is rebuilt from its
+seed. In every golden the frames excused as near a boundary may be at most 10 % of the frames
+(measured on MI355X: see the test's docstring).
+The in-encoder attention and xc2e_attention_relkey (tests/test_gpu_codec_enc_ops.py, against
+fp64 at these lengths) are one launch: semantic() and the entry point both call csrc/xc2enc.hip's
+attention_relkey() with the same kernel, grid and arguments, as the conv module's middle goes
+through conv_module_mid() and every snake through snake_launch().
 Parity against the pip ``xcodec2`` package the reference imports is unpinned (absent)."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,6 +30,7 @@ import torch
 
 from conftest import GOLDEN
 
+sys.path.insert(0, GOLDEN)
 pytestmark = pytest.mark.gpu
 
 
@@ -36,8 +48,14 @@ def _bounded(p, level=4):
     return np.tanh(b + shift) * half_range - offset
 
 
-@pytest.mark.parametrize("name", ["tiny", "full16k"])
+LONG = ["tiny_long", "tiny_t200", "tiny_short", "full16k_mid"]
+
+
+@pytest.mark.parametrize("name", ["tiny", "full16k"] + LONG)
 def test_encoder_vs_transformers_golden(name):
+    """MI355X, the LONG goldens: every id equal (334/334, 200/200, 3/3, 134/134; 10, 5, 0 and 2
+    frames near a boundary), features within 8.1e-5 / 1.3e-5 / 3.3e-6 / 7.6e-5, latents within
+    1.7e-5 / 7.7e-6 / 3.7e-6 / 8.7e-6 x RMS."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from t5gemma_tts_amd.codec_enc import EncoderConfig, XCodec2Encoder, synthetic_encoder_weights
@@ -45,9 +63,15 @@ def test_encoder_vs_transformers_golden(name):
     c = dict(meta["config"])
     c["strides"], c["levels"] = tuple(c["strides"]), tuple(c["levels"])
     cfg = EncoderConfig(**c)
-    enc = XCodec2Encoder(cfg, synthetic_encoder_weights(cfg, meta["weight_seed"]), device="cuda:0", max_seconds=2.0)
-    wav = torch.from_numpy(z["wav"])
-    feat = enc.features(wav).cpu()
+    enc = XCodec2Encoder(cfg, synthetic_encoder_weights(cfg, meta["weight_seed"]), device="cuda:0",
+                         max_seconds=max(2.0, meta["n_samples"] / 16000 + 0.5))
+    if "wav" in z:
+        wav = torch.from_numpy(z["wav"])
+    else:
+        from make_golden_codec_enc import test_wave
+        wav = test_wave(meta["n_samples"], meta["wave_seed"])
+    feat = enc.features(wav).cpu()[::meta.get("feature_row_stride", 1)]
+    assert feat.shape == z["features"].shape
     ferr = (feat - torch.from_numpy(z["features"])).abs().max().item()
     codes, lat = enc.encode(wav, return_latent=True)
     torch.cuda.synchronize()
@@ -64,6 +88,9 @@ def test_encoder_vs_transformers_golden(name):
     assert ferr <= 2e-3, ferr
     assert lerr <= 1e-2, lerr
     assert np.all(same | near), np.nonzero(~same)[0]
+    assert near.sum() <= 0.10 * near.size, (int(near.sum()), near.size)
+    if name in LONG:
+        assert lat.shape[0] == meta["n_codes"] and int(near.sum()) == meta["frames_near_boundary"]
 
 
 def test_audio_tokenizer_encode_and_prompt_from_wav_file(tmp_path):

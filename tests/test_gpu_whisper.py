@@ -8,6 +8,12 @@ dims and at large-v3-turbo dims (128 mels, 32 x 1280 encoder, 4 x 1280 decoder):
   token at a time through the self-attention cache) within 2e-3 x their RMS, argmax equal;
 * detect_language's choice, and the tokens of transcribe(audio, temperature=0) -- the
   host control flow over the GPU logits -- equal to the oracle's.
+* a second teacher-forced sequence that fills the 448-token text context (golden_whisper_*_long:
+  a condition_on_previous_text prompt of 203 tokens, then the longest decode), fed as one
+  prefill plus single steps and again in chunks of 2, 4, 5 and 130: the tiled GEMM in the
+  decoder, causal attention over two query blocks and at an offset, and a self cache whose
+  splits cross 256 keys up to the last row.
+One recognizer per config serves every test of this file (each test sets the state it needs).
 Parity against the openai-whisper package itself is unpinned (absent)."""
 import json
 import os
@@ -30,7 +36,16 @@ def _load(name):
     return meta, dict(np.load(os.path.join(GOLDEN, f"golden_whisper_{name}.npz")))
 
 
+_MODELS = {}
+
+
 def _setup(name, tmp_path):
+    if name not in _MODELS:
+        _MODELS[name] = _build(name, tmp_path)
+    return _MODELS[name]
+
+
+def _build(name, tmp_path):
     from t5gemma_tts_amd import whisper_asr as w
     from make_golden_codec_enc import test_wave
     from whisper_oracle import write_synthetic_tiktoken
@@ -71,6 +86,54 @@ def test_whisper_model_vs_transformers_golden(name, tmp_path):
     assert ferr <= 2e-3, ferr
     assert lerr <= 2e-3, lerr
     assert lg.argmax(-1).tolist() == meta["logit_argmax"]
+
+
+LONG_PASSES = {"prefill_then_steps": [203], "chunks_2_4_5_130_then_steps": [2, 4, 5, 130]}
+
+
+@pytest.mark.parametrize("chunks", list(LONG_PASSES))
+@pytest.mark.parametrize("name", ["tiny", "turbo"])
+def test_whisper_full_context_teacher_forcing(name, chunks, tmp_path):
+    """448 teacher-forced tokens against golden_whisper_<name>_long, at the bound of the short
+    sequence (2e-3 x the logits' RMS). prefill_then_steps: 203 tokens at once (the tiled GEMM,
+    causal attention over two query blocks), then 245 single steps to position 447 (self-cache
+    splits crossing 256 keys with a ragged second split). chunks_...: the same tokens as 2 + 4
+    (the GEMV at M = 2 and 4), 5 + 130 (the tiled GEMM and the causal kernel at q_off > 0), then
+    single steps. The argmax is equal on every row whose golden top-2 margin exceeds twice the
+    bound; the other rows are at most 5 % (4 of 448 in the tiny golden, none in turbo).
+    MI355X: logits within 3.0e-6 / 3.0e-6 x RMS (tiny, the two passes) and 3.8e-6 / 3.9e-6 (turbo),
+    the argmax equal on all 448 rows in all four."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    w, meta, z, m, tok, audio = _setup(name, tmp_path)
+    with open(os.path.join(GOLDEN, f"golden_whisper_{name}_long.json")) as f:
+        lmeta = json.load(f)
+    lz = np.load(os.path.join(GOLDEN, f"golden_whisper_{name}_long.npz"))
+    assert lmeta["weight_seed"] == meta["weight_seed"] and lmeta["audio_seed"] == meta["audio_seed"]
+    toks = lmeta["teacher_tokens"]
+    assert len(toks) == m.dims.n_text_ctx and LONG_PASSES["prefill_then_steps"] == [lmeta["prefill"]]
+    m.log_mel(audio)
+    m.encode(0, lmeta["content_frames"])
+    sub = torch.from_numpy(lz["sub"]).long().cuda()
+    rows, arg, pos = [], [], 0
+    sizes = LONG_PASSES[chunks]
+    for n in sizes + [1] * (len(toks) - sum(sizes)):
+        lg = m.logits(toks[pos:pos + n], pos)
+        rows.append(lg[:, sub].clone())
+        arg.append(lg.argmax(-1))
+        pos += n
+    assert pos == len(toks)
+    got, arg = torch.cat(rows, 0).cpu(), torch.cat(arg, 0).cpu()
+    ref = torch.from_numpy(lz["logits_sub"])
+    rms = ref.pow(2).mean().sqrt().item()
+    lerr = (got - ref).abs().max().item() / rms
+    excused = torch.from_numpy(lz["margin"]) <= 2 * 2e-3 * rms
+    same = arg == torch.from_numpy(lz["argmax"]).long()
+    print(f"{name} {chunks}: logits err/rms {lerr:.2e}, argmax equal {int(same.sum())}/{same.numel()}, "
+          f"{int(excused.sum())} rows within twice the bound")
+    assert lerr <= 2e-3, lerr
+    assert bool((same | excused).all()), torch.nonzero(~(same | excused)).view(-1).tolist()
+    assert int(excused.sum()) == lmeta["rows_within_twice_bound"] and excused.sum() <= 0.05 * excused.numel()
 
 
 @pytest.mark.parametrize("name", ["tiny", "turbo"])

@@ -201,6 +201,80 @@ def test_resid_norm_src_out_rows_with_slabs_is_unsupported():
     assert _lib.lib().t5g_resid_norm_src(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
 
 
+def _op(name, table):
+    from t5gemma_tts_amd import _lib
+    fn = getattr(_lib.lib(), name)
+    fn.restype, fn.argtypes = table[name]
+    return fn
+
+
+def _refused(fn, good, kw):
+    """The call with `kw` over the valid arguments `good` (pointers are never dereferenced: the
+    valid call itself is never made) returns -1."""
+    a = dict(good)
+    a.update(kw)
+    return fn(*a.values()) == -1
+
+
+_IDS = dict(ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+
+
+@pytest.mark.parametrize("kw", [dict(qkv=None), dict(qe=None), dict(out=None), dict(T=0), dict(T=-5), dict(heads=0),
+                                dict(heads=-2), dict(L=-1), dict(R=-1)], **_IDS)
+def test_xc2e_attention_relkey_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd.codec_enc import XC2E_SIGNATURES
+    good = dict(qkv=16, T=42, heads=2, qe=16, L=64, R=8, out=16, stream=None)
+    assert _refused(_op("xc2e_attention_relkey", XC2E_SIGNATURES), good, kw)
+
+
+@pytest.mark.parametrize("kw", [dict(x=None), dict(alpha=None), dict(beta=None), dict(up=None), dict(down=None),
+                                dict(y=None), dict(T=0), dict(C=0), dict(C=-1), dict(form=2), dict(form=-1),
+                                dict(T=1 << 20, C=1 << 12)], **_IDS)
+def test_xc2e_snake_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd.codec_enc import XC2E_SIGNATURES
+    good = dict(x=16, T=12, C=5, alpha=16, beta=16, up=16, down=16, y=16, form=0, stream=None)
+    assert _refused(_op("xc2e_snake", XC2E_SIGNATURES), good, kw)
+
+
+@pytest.mark.parametrize("kw", [dict(p1=None), dict(dw=None), dict(ln_w=None), dict(ln_b=None), dict(out=None),
+                                dict(T=0), dict(H=0), dict(H=126), dict(H=1028), dict(H=2048), dict(KW=0),
+                                dict(KW=-31)], **_IDS)
+def test_xc2e_conv_module_mid_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd.codec_enc import XC2E_SIGNATURES
+    good = dict(p1=16, T=42, H=128, KW=31, dw=16, ln_w=16, ln_b=16, eps=1e-5, out=16, stream=None)
+    assert _refused(_op("xc2e_conv_module_mid", XC2E_SIGNATURES), good, kw)
+
+
+@pytest.mark.parametrize("kw", [dict(m=None), dict(Q=None), dict(K=None), dict(V=None), dict(O=None), dict(Tq=0),
+                                dict(Tk=0), dict(q_off=-1), dict(causal=2), dict(ldkv=0), dict(ldkv=130),
+                                # a key / value width that is not 64 x heads or more
+                                dict(ldkv=64), dict(ldkv=124),
+                                # causal: the last query's range ends inside the keys
+                                dict(q_off=7), dict(Tq=11, q_off=0),
+                                # one query: all keys count, and the split workspace holds 1500
+                                dict(Tq=1, Tk=10, q_off=3), dict(Tq=1, Tk=1501, causal=0, q_off=0)], **_IDS)
+def test_whs_attention_op_rejects_bad_arguments(kw):
+    """The checks read only the model's leading whs_config (head count, the two context lengths),
+    so a host buffer that starts with one stands in for a model: creating a real one needs the
+    GPU, and every case here is refused before a launch."""
+    from t5gemma_tts_amd import whisper_asr as w
+    cfg = w.WHSConfig(n_mels=80, n_audio_ctx=1500, n_audio_state=128, n_audio_head=2, n_audio_layer=2, n_vocab=51866,
+                      n_text_ctx=448, n_text_state=128, n_text_head=2, n_text_layer=2, max_samples=16000)
+    standin = C.create_string_buffer(bytes(cfg), C.sizeof(cfg) + C.sizeof(w.WHSWeights) + 1024)
+    good = dict(m=C.addressof(standin), Q=16, K=16, V=16, ldkv=128, Tq=4, Tk=10, causal=1, q_off=6, O=16, stream=None)
+    assert _refused(_op("whs_attention_op", w.WHS_SIGNATURES), good, kw)
+
+
+@pytest.mark.parametrize("kw", [dict(X=None), dict(W=None), dict(Y=None), dict(M=0), dict(N=0), dict(K=0), dict(K=-4),
+                                dict(epi=1), dict(epi=5), dict(epi=-1),
+                                # the tiled GEMM's K step is 32: M > 4 or K % 4 != 0 lands there
+                                dict(M=5, K=2052), dict(K=130), dict(M=5, K=130)], **_IDS)
+def test_whs_linear_op_rejects_bad_arguments(kw):
+    from t5gemma_tts_amd import whisper_asr as w
+    good = dict(X=16, M=2, W=16, N=128, K=128, bias=None, resid=None, epi=0, Y=16, stream=None)
+    assert _refused(_op("whs_linear_op", w.WHS_SIGNATURES), good, kw)
+
+
 def test_status_codes_map_to_python_errors():
     """The C ABI's statuses raise what the reference's code paths would (ValueError for bad
     arguments / capacity) and a FusedHandoffError for a fused decode launch whose hand-off
