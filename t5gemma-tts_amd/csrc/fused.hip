@@ -394,7 +394,9 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
 // front of the three MLP-half launches, with the same arithmetic in every stage (bitwise
 // equal to the seven launches: tests/test_gpu_fused.py). Every wave requests the weights
 // of a stage as early as its registers allow: Q's before N1 completes, O's during the
-// attention, gate/up's right after O (norm workgroups: after N2), down's after gate/up;
+// attention, gate/up's right after O (norm workgroups: after N2), down's after gate/up (one
+// tile: the waves that store nothing in gate/up's epilogue right after its MFMAs, the storing
+// waves after the publish);
 // the cross K / V of the attention workgroups and their RoPE table at launch start.
 // Round 5 adds the layer's decode self attention as stage S (fb_self_attn, the flash launch's
 // arithmetic): fused_block_kernel<1> runs it in front of O1; fused_block_kernel<2> runs the
@@ -427,10 +429,18 @@ __device__ __forceinline__ void fb_issue(bf16x8_s (&w)[UMAX][SPU], const bf16_t*
 // same order as from registers. MT: 16-row MFMA tiles (rows 16 t + lane % 16; every tile takes
 // the same weights through the same per-wave k-step chain, its partial sums in its own part of
 // `red`: unit i, tile t at (i MT + t) x NWG KiB).
-template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false, int MT = 1>
+//
+// `mid` runs at the split between the two parts -- the MFMA part (rendezvous, X fragments,
+// MFMAs, partial sums to `red`, barrier) and the epilogue part (fixed-order reduction,
+// epilogue, stores) -- and a wave for which it returns true skips the epilogue: a one-tile
+// stage has the waves that store nothing (wave >= nu) request the next stage's weights there.
+struct FbNoMid {
+    __device__ __forceinline__ bool operator()() const { return false; }
+};
+template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false, int MT = 1, typename Mid = FbNoMid>
 __device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int gs, int nu, int kb_lo, int KBs,
                                           const bf16_t* X, int ldx, int xbytes, int M, void* Y, int ldy, int ybytes,
-                                          int N, f32x4* red, const char* lw = nullptr, int nu_reg = 0) {
+                                          int N, f32x4* red, const char* lw = nullptr, int nu_reg = 0, Mid mid = Mid()) {
     static_assert(MT == 1 || (!LDSU && EPI != EPI_GEGLU), "the LDS unit and the GeGLU epilogue are one-tile only");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int xr = lane & 15;
@@ -472,6 +482,7 @@ __device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int 
         }
     }
     __syncthreads();
+    if (mid()) return;
     constexpr bool GLU = EPI == EPI_GEGLU;
     const int n_out = GLU ? N / 2 : N;
     if (wave >= NWG || (MT == 1 && xr >= M) || (GLU && lane >= 32)) return;
@@ -1403,25 +1414,47 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
 
     // ---- G: gate/up, contiguous unit runs over the workers (<= 5 units; the last from LDS
     // on the workers that fetched it)
+    //
+    // One tile: a wave that stores nothing in G's epilogue (wave >= nu_g, a scalar so the two
+    // sides are real branches) requests its down weights right after G's MFMAs, under the storing
+    // waves' epilogue, drain and publish. Only the storing waves drain, and the barrier in front
+    // of the publish is the raw one: the early requests stay in flight across it. wg is dead by
+    // then, so no two weight arrays are live in any MFMA.
+    bf16x8_s wd[5][3];
+    bool d_early = false;
     if constexpr (MT == 1) {
         bf16x8_s wg[5][6];
         const int nu_r = gu_lds ? nu_g - 1 : nu_g;
         fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u);
         T5G_TS(3);
+        const int dper = nw / FM_DS, s = w / dper, j = w - s * dper;   // D's mapping (below)
+        d_early = s < FM_DS && __builtin_amdgcn_readfirstlane(wave) >= nu_g;
         fb_finish<FM_NW, EPI_GEGLU, 6, 5, 0, true>(wg, g_lo, 1, nu_g, 0, KBg, a.xn, d, M * d * 2, M, a.act, f,
-                                                   M * f * 2, 2 * f, red, gul, nu_r);
+                                                   M * f * 2, 2 * f, red, gul, nu_r, [&]() {
+                                                       if (!d_early) return false;
+                                                       const int KBd = f / 32, per = KBd / FM_DS;
+                                                       fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper,
+                                                                             (a.NGd - j + dper - 1) / dper);
+                                                       return true;
+                                                   });
+        T5G_TS(4);
+        if (!d_early) drain_vm();   // act stores of the storing waves (R1)
     } else {
         // two tiles: fused_mlp_kernel<2>'s stage (units streamed two batches deep, both tiles'
         // partial sums in `red`), the first unit requested before the N2 wait
         ok &= fm_gemv<MT, EPI_GEGLU, 6, 0>(
             a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, M * d * 2, M, a.act, f, M * f * 2, 2 * f, red,
             [&]() { return fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u); }, [](int) {}, 3);
+        T5G_TS(4);
     }
-    T5G_TS(4);
     const int units_per_slice = f / FM_DS / 8;
-    drain_vm();
-    __syncthreads();
+    if constexpr (MT == 1) {
+        wg_barrier();   // every storing wave has drained; the early requests stay in flight
+    } else {
+        drain_vm();
+        __syncthreads();
+    }
     if (tq == 0 && nu_g > 0) {
         const int s0 = g_lo / units_per_slice, s1 = (g_lo + nu_g - 1) / units_per_slice;
         for (int sl = s0; sl <= s1; ++sl) {
@@ -1435,8 +1468,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     if (s < FM_DS) {
         const int KBd = f / 32, per = KBd / FM_DS;
         const int nu_d = (a.NGd - j + dper - 1) / dper;
-        bf16x8_s wd[5][3];
-        fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper, nu_d);
+        if (!d_early) fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper, nu_d);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_SL0 + s, (unsigned)units_per_slice, tmo, 6u + s);
         T5G_TS(5);
         fb_finish<FM_NW, EPI_F32, 3, 5, 2, false, MT>(wd, j, dper, nu_d, s * per, per, a.act, f, M * f * 2, M,
