@@ -394,7 +394,8 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
 // front of the three MLP-half launches, with the same arithmetic in every stage (bitwise
 // equal to the seven launches: tests/test_gpu_fused.py). Every wave requests the weights
 // of a stage as early as its registers allow: Q's before N1 completes, O's during the
-// attention, gate/up's right after O (norm workgroups: after N2), down's after gate/up (one
+// attention, gate/up's right after O (norm workgroups: after N2; one tile: waves 8-10 of the
+// workers without an attention task, idle from Q to G, with the LDS copies), down's after gate/up (one
 // tile: the waves that store nothing in gate/up's epilogue right after its MFMAs, the storing
 // waves after the publish);
 // the cross K / V of the attention workgroups and their RoPE table at launch start.
@@ -1277,6 +1278,17 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     // into LDS: 24 x 1 KiB each, no registers, while the attention workers run A (on an
     // attention worker the copies would queue ahead of its q loads). O's publish drains
     // them (vmcnt); its barrier makes them visible to the other waves.
+    //
+    // The same waves hold nothing else until G (O1, A and O are 8-wave or 4-wave stages), so
+    // they request their share of the run's register units (wg: k-steps wave + 12 j) here as
+    // well, ~8 us before O's hand-off while HBM is mostly idle, and skip the request at G's
+    // entry. g_early is a scalar, so both sides are real branches: these waves cross O on its
+    // barriers alone (O's code with wg live is never theirs), and O's publish drains their
+    // requests with the LDS copies. Wave 11 polls in O and requests nothing early.
+    bf16x8_s wg[5][6];
+    const int nu_r = gu_lds ? nu_g - 1 : nu_g;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const bool g_early = MT == 1 && gu_lds && swave >= 8 && swave < 11;
     if (gu_lds && wave >= 8 && wave < 11) {
         const int wv = __builtin_amdgcn_readfirstlane(wave - 8);
         const __amdgpu_buffer_rsrc_t gr = frag_rsrc(a.Wgu, (uint32_t)NGg * (uint32_t)KBg * 1024u);
@@ -1287,129 +1299,138 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         for (int q = 0; q < FB_GU_KB / 3; ++q)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(gr, dst + q * 1024, 16, gb + q * 1024, 0, 0, AUX_NT);
     }
+    if (g_early) {
+        fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
+        if (owork) {          // O's rendezvous for a wave with no part in it:
+            wg_barrier();     // fb_finish's hand-off barrier,
+            __syncthreads();  // the barrier that closes its MFMA part,
+            drain_vm();       // and fb_publish (the LDS unit and wg have landed)
+            __syncthreads();
+        }
+    } else {
+        // ---- A (attention workers) with O's weight requests around it
+        // (two tiles: waves 4-7 run the pair's second head, so O's requests follow the attention)
+        bf16x8_s wo[3][2];
+        if (MT == 1 && attnwg && wave >= 4 && owork) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+        if (attnwg) {
+            const int qcnt = 2 * (D / 16);   // 16 q units per head x 2 k-slices
+            // (wave 0's head is the pair's first: two tiles poll both heads' lines at once)
+            if (wave == 0) ok &= fm_wait_n<MT>(a.sync, L_Q0 + ah, (unsigned)qcnt, tmo, 2u);
+            wg_barrier();
+            const int n = alen;
+            const int span = alen;
+            if (tq < 256 * MT) {
+                const int c4 = at < D / 4 ? at : 0;
+                const int col = ah * D + 4 * c4;
+                const __amdgpu_buffer_rsrc_t qr = raw_rsrc(a.qslab, (uint32_t)(2 * M * a.q_dim * 4));
+                const f32x4 u0 = __builtin_bit_cast(
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, (am * a.q_dim + col) * 4, 0, AUX_SC1));
+                const f32x4 u1 = __builtin_bit_cast(
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, ((M + am) * a.q_dim + col) * 4, 0, AUX_SC1));
+                const f32x4 acc = u0 + u1;
+                if (at < D / 4) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) al.qs[4 * c4 + jj] = rbf(acc[jj]);
+                }
+            }
+            fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
+            if (tq < 256 * MT) {
+                float q[8];
+                const float sg = dl < LPK / 2 ? -1.0f : 1.0f;
+                const int pbase = (8 * dl + D / 2) % D;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    const float x = al.qs[8 * dl + jj];
+                    const float pr = al.qs[pbase + jj];
+                    q[jj] = rbf(rbf(x * c8[jj]) + rbf((sg * pr) * s8[jj]));
+                }
+#pragma unroll
+                for (int i = 0; i < NIT; ++i) {
+                    const int j = i * KPB + aw * KPW + kg;
+                    if (j >= n) {
+                        kr[i] = (u32x4){0u, 0u, 0u, 0u};
+                        vr[i] = (u32x4){0u, 0u, 0u, 0u};
+                    }
+                }
+                // every key's reduction before any store (they overlap), exchanges on the VALU
+                float scs[NIT];
+#pragma unroll
+                for (int i = 0; i < NIT; ++i) {
+                    float sc = 0.f;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const float k0 = bf_lo(kr[i][jj]), k1 = bf_hi(kr[i][jj]);
+                        sc += q[2 * jj] * k0 + q[2 * jj + 1] * k1;
+                    }
+                    scs[i] = xsum_v<LPK>(sc);   // xsum<LPK>'s adds
+                }
+                if (dl == 0) {
+#pragma unroll
+                    for (int i = 0; i < NIT; ++i) al.sm[i * KPB + aw * KPW + kg] = fast_score(scs[i], a.scale, a.softcap);
+                }
+            }
+            fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
+            if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {   // a head's first wave
+                const float sc = lane < n ? al.sm[lane] : -INFINITY;
+                const float p = one_block_p(sc, lane < n, lane, span);
+                al.pl[lane] = p;
+                if (lane < 16) al.pl[64 + lane] = 0.f;
+                al.sm[lane] = rbf(p);
+                __builtin_amdgcn_wave_barrier();
+                const float l = sdpa_block_sum_lds<64>(al.pl, span, lane);
+                if (lane == 0) al.stat_l = l;
+            }
+            fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
+            if (tq < 256 * MT) {
+                float o[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) o[jj] = 0.f;
+#pragma unroll
+                for (int i = 0; i < NIT; ++i) {
+                    const int jl = i * KPB + aw * KPW + kg;
+                    const float p = al.sm[jl];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        o[2 * jj] += p * bf_lo(vr[i][jj]);
+                        o[2 * jj + 1] += p * bf_hi(vr[i][jj]);
+                    }
+                }
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) o[jj] += xlane32_v(o[jj]);   // LPK = 32: one xor-32 step
+                if (kg == 0) {
+                    al.ored[aw][dl][0] = (f32x4){o[0], o[1], o[2], o[3]};
+                    al.ored[aw][dl][1] = (f32x4){o[4], o[5], o[6], o[7]};
+                }
+            }
+            fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
+            if ((MT == 1 ? tq < LPK : (tq & ~256) < LPK) && n > 0) {
+                const int d8 = at;
+                // (attn_chunk.h fold_ored's order; called here, the two-tile kernels' schedule moves)
+                const f32x4 lo4 = al.ored[0][d8][0] + al.ored[1][d8][0] + al.ored[2][d8][0] + al.ored[3][d8][0];
+                const f32x4 hi4 = al.ored[0][d8][1] + al.ored[1][d8][1] + al.ored[2][d8][1] + al.ored[3][d8][1];
+                const u32x4 w = normalise_pack(lo4, hi4, al.stat_l);
+                const __amdgpu_buffer_rsrc_t orr = raw_rsrc(a.att, (uint32_t)(M * a.q_dim * 2));
+                __builtin_amdgcn_raw_buffer_store_b128(w, orr, (am * a.q_dim + ah * D + 8 * d8) * 2, 0, AUX_SC1);
+            }
+            // only a head's first wave stored: it drains and publishes (the other waves' O weight
+            // requests stay in flight)
+            if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {
+                drain_vm();
+                if (lane == 0) __hip_atomic_fetch_add(cline(a.sync, L_A0 + ah), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
 
-    // ---- A (attention workers) with O's weight requests around it
-    // (two tiles: waves 4-7 run the pair's second head, so O's requests follow the attention)
-    bf16x8_s wo[3][2];
-    if (MT == 1 && attnwg && wave >= 4 && owork) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
-    if (attnwg) {
-        const int qcnt = 2 * (D / 16);   // 16 q units per head x 2 k-slices
-        // (wave 0's head is the pair's first: two tiles poll both heads' lines at once)
-        if (wave == 0) ok &= fm_wait_n<MT>(a.sync, L_Q0 + ah, (unsigned)qcnt, tmo, 2u);
-        wg_barrier();
-        const int n = alen;
-        const int span = alen;
-        if (tq < 256 * MT) {
-            const int c4 = at < D / 4 ? at : 0;
-            const int col = ah * D + 4 * c4;
-            const __amdgpu_buffer_rsrc_t qr = raw_rsrc(a.qslab, (uint32_t)(2 * M * a.q_dim * 4));
-            const f32x4 u0 = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, (am * a.q_dim + col) * 4, 0, AUX_SC1));
-            const f32x4 u1 = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, ((M + am) * a.q_dim + col) * 4, 0, AUX_SC1));
-            const f32x4 acc = u0 + u1;
-            if (at < D / 4) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) al.qs[4 * c4 + jj] = rbf(acc[jj]);
-            }
+        // ---- O: cross-o, 4 k-slices of 16 k-steps over nw / 4 workers each (<= 3 units, 8 waves)
+        if (owork) {
+            // waves 0-7 (the GEMV) request their weights first; wave 11, idle in this stage and
+            // with nothing queued, polls the 8 q heads
+            if (!(MT == 1 && attnwg && wave >= 4)) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+            if (wave == FM_NW - 1) ok &= fm_wait_n<8>(a.sync, L_A0, (unsigned)M, tmo, 3u);
+            T5G_TS_BY(2, (FM_NW - 1) * 64);
+            fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
+                                           a.oslab + (long)so * M * d, d, M * d * 4, d, red);
+            fb_publish(cline(a.sync, L_O0 + (w & 7)), 1u);
         }
-        fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (tq < 256 * MT) {
-            float q[8];
-            const float sg = dl < LPK / 2 ? -1.0f : 1.0f;
-            const int pbase = (8 * dl + D / 2) % D;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                const float x = al.qs[8 * dl + jj];
-                const float pr = al.qs[pbase + jj];
-                q[jj] = rbf(rbf(x * c8[jj]) + rbf((sg * pr) * s8[jj]));
-            }
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int j = i * KPB + aw * KPW + kg;
-                if (j >= n) {
-                    kr[i] = (u32x4){0u, 0u, 0u, 0u};
-                    vr[i] = (u32x4){0u, 0u, 0u, 0u};
-                }
-            }
-            // every key's reduction before any store (they overlap), exchanges on the VALU
-            float scs[NIT];
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                float sc = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const float k0 = bf_lo(kr[i][jj]), k1 = bf_hi(kr[i][jj]);
-                    sc += q[2 * jj] * k0 + q[2 * jj + 1] * k1;
-                }
-                scs[i] = xsum_v<LPK>(sc);   // xsum<LPK>'s adds
-            }
-            if (dl == 0) {
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) al.sm[i * KPB + aw * KPW + kg] = fast_score(scs[i], a.scale, a.softcap);
-            }
-        }
-        fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {   // a head's first wave
-            const float sc = lane < n ? al.sm[lane] : -INFINITY;
-            const float p = one_block_p(sc, lane < n, lane, span);
-            al.pl[lane] = p;
-            if (lane < 16) al.pl[64 + lane] = 0.f;
-            al.sm[lane] = rbf(p);
-            __builtin_amdgcn_wave_barrier();
-            const float l = sdpa_block_sum_lds<64>(al.pl, span, lane);
-            if (lane == 0) al.stat_l = l;
-        }
-        fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if (tq < 256 * MT) {
-            float o[8];
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) o[jj] = 0.f;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int jl = i * KPB + aw * KPW + kg;
-                const float p = al.sm[jl];
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    o[2 * jj] += p * bf_lo(vr[i][jj]);
-                    o[2 * jj + 1] += p * bf_hi(vr[i][jj]);
-                }
-            }
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) o[jj] += xlane32_v(o[jj]);   // LPK = 32: one xor-32 step
-            if (kg == 0) {
-                al.ored[aw][dl][0] = (f32x4){o[0], o[1], o[2], o[3]};
-                al.ored[aw][dl][1] = (f32x4){o[4], o[5], o[6], o[7]};
-            }
-        }
-        fb_lds_barrier();   // LDS only: waves 4-7 keep their O weights in flight
-        if ((MT == 1 ? tq < LPK : (tq & ~256) < LPK) && n > 0) {
-            const int d8 = at;
-            // (attn_chunk.h fold_ored's order; called here, the two-tile kernels' schedule moves)
-            const f32x4 lo4 = al.ored[0][d8][0] + al.ored[1][d8][0] + al.ored[2][d8][0] + al.ored[3][d8][0];
-            const f32x4 hi4 = al.ored[0][d8][1] + al.ored[1][d8][1] + al.ored[2][d8][1] + al.ored[3][d8][1];
-            const u32x4 w = normalise_pack(lo4, hi4, al.stat_l);
-            const __amdgpu_buffer_rsrc_t orr = raw_rsrc(a.att, (uint32_t)(M * a.q_dim * 2));
-            __builtin_amdgcn_raw_buffer_store_b128(w, orr, (am * a.q_dim + ah * D + 8 * d8) * 2, 0, AUX_SC1);
-        }
-        // only a head's first wave stored: it drains and publishes (the other waves' O weight
-        // requests stay in flight)
-        if (MT == 1 ? wave == 0 : (wave & ~4) == 0) {
-            drain_vm();
-            if (lane == 0) __hip_atomic_fetch_add(cline(a.sync, L_A0 + ah), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-
-    // ---- O: cross-o, 4 k-slices of 16 k-steps over nw / 4 workers each (<= 3 units, 8 waves)
-    if (owork) {
-        // waves 0-7 (the GEMV) request their weights first; wave 11, idle in this stage and
-        // with nothing queued, polls the 8 q heads
-        if (!(MT == 1 && attnwg && wave >= 4)) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
-        if (wave == FM_NW - 1) ok &= fm_wait_n<8>(a.sync, L_A0, (unsigned)M, tmo, 3u);
-        T5G_TS_BY(2, (FM_NW - 1) * 64);
-        fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
-                                       a.oslab + (long)so * M * d, d, M * d * 4, d, red);
-        fb_publish(cline(a.sync, L_O0 + (w & 7)), 1u);
     }
 
     // ---- G: gate/up, contiguous unit runs over the workers (<= 5 units; the last from LDS
@@ -1423,9 +1444,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     bf16x8_s wd[5][3];
     bool d_early = false;
     if constexpr (MT == 1) {
-        bf16x8_s wg[5][6];
-        const int nu_r = gu_lds ? nu_g - 1 : nu_g;
-        fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
+        if (!g_early) fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u);
         T5G_TS(3);
         const int dper = nw / FM_DS, s = w / dper, j = w - s * dper;   // D's mapping (below)

@@ -4,7 +4,8 @@ time from the first block start (100 MHz device clock), over all workgroups and 
 norm workgroups. B <= 16 runs fused_block_kernel (points: 1 Q hand-off seen, 2 O hand-off
 seen, 3 G hand-off seen, 4 gate/up published, 5 D hand-off seen, 6 leaving); B > 16
 fused_mlp_kernel (1 norm published, 2 gate/up hand-off seen, 3 gate/up sums in LDS, 4 down
-hand-off seen, 5 down sums in LDS, 6 leaving).
+hand-off seen, 5 down sums in LDS, 6 leaving). B <= 16 also splits points 3-5 by worker class:
+attention workers and the others by the length of their gate/up run.
     python t5gemma-tts_amd/build.py --dbg && T5G_LIB=$PWD/t5gemma-tts_amd/lib/libt5gtts_dbg.so \\
         python tools/diag_fused.py"""
 import ctypes as C
@@ -68,6 +69,24 @@ def main():
         if (norm & ok).any() and (k > 1 or B <= 16):
             en = (v[norm & ok] - base) * 10
             print(f"      norm workgroups: p50 {int(np.median(en))} max {int(en.max())} ns")
+    if B <= 16:
+        # points 3-5 by what a worker has to fetch after cross-o: the attention workers (no
+        # gate/up unit in LDS) and the others by the length of their run (the kernel's map: the
+        # first NG % nw workers one unit more)
+        nw, n_att, ng = nb - B, B * cfg.backbone.num_attention_heads, cfg.backbone.intermediate_size // 8
+        cls = np.full(4096, "norm", dtype=object)
+        for w in range(nw):
+            n = ng // nw + (1 if w < ng % nw else 0)
+            cls[w] = f"attention, {n} units" if w < n_att else f"other, {n} units (1 in LDS)"
+        wg = np.nonzero(a[:, 0] > 0)[0]   # workgroup w's record is row w (dbg_seq 0)
+        print("  gate/up runs: " + ", ".join(f"{int((cls[:nw] == c).sum())} x {c}" for c in sorted(set(cls[:nw]))))
+        for k in (3, 4, 5):
+            v = rows[:, k].astype(np.int64)
+            for c in sorted(set(cls[:nw])):
+                sel = (cls[wg] == c) & (v > 0)
+                if sel.any():
+                    pc = np.percentile((v[sel] - base) * 10, [0, 50, 90, 100]).astype(int)
+                    print(f"  point {k} {c:28s}: min {pc[0]} p50 {pc[1]} p90 {pc[2]} max {pc[3]} ns [{int(sel.sum())}]")
     xcc = (rows[:, 7] >> 32) & 0xf
     for k in (3, 6):
         v = (rows[:, k].astype(np.int64) - base) * 10
