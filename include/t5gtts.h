@@ -164,11 +164,16 @@ int64_t t5g_engine_workspace_bytes(const t5g_engine* e);
  * the host arrays are copied. NULL turns FP8 off. Needs the widths the register-X GEMV sites
  * are built for (hidden 2304, intermediate 9216, q_dim 2048; else T5G_EUNSUPPORTED); refused
  * in parity mode, and t5g_engine_set_exact(e, 1, ...) on an FP8 engine is T5G_EUNSUPPORTED.
- * In FP8 mode every decode batch (1-32 rows) runs the per-op launches with the P8 GEMVs and
- * the head on the P8 GEMV: the persistent layer launches are built for bf16 weights only, so
- * t5g_engine_set_fused does not change an FP8 engine's launches and t5g_time_decode_layer /
- * t5g_time_decode_mlp are T5G_EUNSUPPORTED. More than 32 rows: the bf16 kernels on W_q.
- * No reference-side equivalent. */
+ * Launches in FP8 mode: by default every decode batch (1-32 rows) runs the per-op launches with
+ * the P8 GEMVs, and the head on the P8 GEMV. After t5g_engine_set_fp8_block(e, 1) batches of
+ * 1-16 rows run the whole-layer persistent launch on the P8 images (csrc/fused_p8.hip: all
+ * seven weights of a launch are P8), under the switches and stage-S placement rules of the
+ * bf16 launch (t5g_engine_set_fused, t5g_engine_set_attn_in_block); layer 0's q|k|v, attention
+ * and o-projection and the head stay on the P8 GEMVs, and 17-32 rows stay on the per-op P8
+ * launches whatever t5g_engine_set_block_max_rows says (there is no P8 form of the two-tile or
+ * the MLP-half launch). t5g_time_decode_layer serves an FP8 engine only with that switch on and
+ * <= 16 rows (else T5G_EUNSUPPORTED); t5g_time_decode_mlp is T5G_EUNSUPPORTED in FP8 mode.
+ * More than 32 rows: the bf16 kernels on W_q. No reference-side equivalent. */
 typedef struct {
     const void* p8;        /* P8 codes, t5g_fp8_packed_bytes(N, K) bytes */
     const float* scale;    /* fp32 [16 * ceil(N / 16)] */
@@ -183,6 +188,12 @@ typedef struct {
 int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* w);
 /* *fmt = 0: bf16 weights, 1: FP8 mode. No reference-side equivalent. */
 int t5g_engine_weight_format(t5g_engine* e, int32_t* fmt);
+/* FP8 mode: let decode batches of 1-16 rows run the whole-layer persistent launch on the P8
+ * images (see above). Default 0. Bitwise equal to the per-op P8 launches and to the bf16
+ * launch on W_q (tests/test_gpu_fp8_block.py). T5G_EINVAL on a NULL engine; enabling on an
+ * engine that is not in FP8 mode is T5G_EUNSUPPORTED (t5g_engine_set_fp8_weights(e, NULL)
+ * also clears the switch). A change drops the captured graphs. No reference-side equivalent. */
+int t5g_engine_set_fp8_block(t5g_engine* e, int32_t enable);
 
 /* --- generate() phases --------------------------------------------------------
  * Token batches are PACKED: ntok tokens of B rows, with per-token row index

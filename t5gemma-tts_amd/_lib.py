@@ -182,6 +182,7 @@ SIGNATURES = {
     "t5g_engine_set_sampler_path": (C.c_int, [_P, _I]),
     "t5g_engine_set_fused": (C.c_int, [_P, _I]),
     "t5g_engine_set_block_max_rows": (C.c_int, [_P, _I]),
+    "t5g_engine_set_fp8_block": (C.c_int, [_P, _I]),
     "t5g_engine_block_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_engine_xlayer_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_time_xlayer": (C.c_int, [_P, _I, _I, _P, C.POINTER(C.c_float)]),
@@ -311,13 +312,13 @@ T5G_EUNSUPPORTED = -3
 # digest when the pass runs, and bench.py quotes that file's traffic only while the sources
 # still hash the same (a kernel change that keeps the kernel's name makes the file stale)
 PMC_SOURCES = {
-    "fused_block": ["fused.hip", "attn_chunk.h", "common.h", "t5g_kernels.h"],
-    "fused_block_s": ["fused.hip", "attn_chunk.h", "common.h", "t5g_kernels.h"],
-    "fused_mlp": ["fused.hip", "common.h", "t5g_kernels.h"],
+    "fused_block": ["fused.hip", "fused_p8.hip", "fp8.h", "attn_chunk.h", "common.h", "t5g_kernels.h"],
+    "fused_block_s": ["fused.hip", "fused_p8.hip", "fp8.h", "attn_chunk.h", "common.h", "t5g_kernels.h"],
+    "fused_mlp": ["fused.hip", "fused_p8.hip", "fp8.h", "common.h", "t5g_kernels.h"],
     "xlayer": ["xlayer.hip", "exact_dev.h", "exact_math.h", "common.h", "t5g_kernels.h"],
     "gate_up": ["gemv.hip", "common.h", "t5g_kernels.h"],
     # every source the fast decode step's logits and tokens depend on (fast_token_agreement)
-    "fast_path": ["fused.hip", "attn.hip", "attn_chunk.h", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
+    "fast_path": ["fused.hip", "fused_p8.hip", "attn.hip", "attn_chunk.h", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
                   "engine.hip", "engine_state.h", "common.h", "t5g_kernels.h"],
 }
 
@@ -382,7 +383,7 @@ def xlayer_bytes(B: int, bb, text_len: int, n_layers: int) -> float:
 
 
 def fused_block_bytes(M: int, T_x: int, d: int = 2304, f: int = 9216, q_dim: int = 2048, kv_dim: int = 1024,
-                      n_layers: int = 26, self_keys: float = 0.0) -> float:
+                      n_layers: int = 26, self_keys: float = 0.0, weight_format: str = "bf16") -> float:
     """Algorithmic HBM bytes of one fused_block_kernel launch, averaged over a step's layers (the
     last layer projects no next q|k|v): self o, cross q / o, gate/up, down and the next layer's
     q|k|v weights; the self-attention output, h, the six norm weights, the rows' cross K / V
@@ -392,14 +393,23 @@ def fused_block_bytes(M: int, T_x: int, d: int = 2304, f: int = 9216, q_dim: int
     self_keys > 0: the launch runs the self attention as its stage S (t5g_time_decode_layer's
     keys: per kv head, summed over the rows, averaged over the layers) -- the cached K / V
     rows read (the appended one is computed, not read), the appended key / value written, the
-    layer's q|k|v slabs in; the attention output becomes an in-launch hand-off."""
+    layer's q|k|v slabs in; the attention output becomes an in-launch hand-off.
+    weight_format "fp8" (the P8 launch, csrc/fused_p8.hip): each weight counts 1 byte per
+    element plus its fp32 row scales (4 bytes per output row) instead of 2 bytes per element."""
+    if weight_format not in ("bf16", "fp8"):
+        raise ValueError(f"weight_format {weight_format!r}: 'bf16' or 'fp8'")
     qkv_dim = q_dim + 2 * kv_dim
     base = 3 * q_dim * d * 2 + 2 * f * d * 2 + d * f * 2   # self o, cross q, cross o, gate/up, down
+    w_qkv = qkv_dim * d * 2
+    if weight_format == "fp8":
+        # output rows: self o d, cross q q_dim, cross o d, gate/up 2 f, down d; next q|k|v qkv_dim
+        base = base // 2 + 4 * (d + q_dim + d + 2 * f + d)
+        w_qkv = w_qkv // 2 + 4 * qkv_dim
     att_in = M * q_dim * 2
     if self_keys > 0:
         att_in = (self_keys - M) * kv_dim * 2 * 2 + M * kv_dim * 2 * 2 + 2 * M * qkv_dim * 4
     base += att_in + M * d * 2 + 6 * d * 2 + M * T_x * 2 * kv_dim * 2 + M * 256 * 4 + M * d * 2
-    mid = base + qkv_dim * d * 2 + 2 * M * qkv_dim * 4
+    mid = base + w_qkv + 2 * M * qkv_dim * 4
     last = base + M * d * 2
     return ((n_layers - 1) * mid + last) / n_layers
 

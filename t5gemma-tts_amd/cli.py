@@ -90,14 +90,16 @@ def load_codec(codec_dir: Optional[str] = None, codec: str = "44k", device="cuda
 
 
 def load_model(model_dir: Optional[str] = None, synthetic: Optional[str] = None, device="cuda:0",
-               max_text: int = 512, max_audio: Optional[int] = None, seed: int = 7, weight_format: str = "bf16"):
+               max_text: int = 512, max_audio: Optional[int] = None, seed: int = 7, weight_format: str = "bf16",
+               fp8_block: bool = False):
     """The voice model, sized for the reference CLI's longest request by default (max_audio =
     engine.MAX_AUDIO keys: a 100 s prompt + the 120 s duration cap; 1.3 GB of KV cache at
     batch 1) -- a shorter request runs on its own key bound, not the capacity.
-    ``weight_format="fp8"``: the decode step streams FP8 e4m3 weights (fast path only)."""
+    ``weight_format="fp8"``: the decode step streams FP8 e4m3 weights (fast path only);
+    ``fp8_block=True`` with it: the whole-layer decode launch on those weights (default off)."""
     from .engine import MAX_AUDIO, T5GemmaVoiceForConditionalGeneration
     kw = dict(device=device, max_batch=1, max_text=max_text, max_audio=MAX_AUDIO if max_audio is None else max_audio,
-              weight_format=weight_format)
+              weight_format=weight_format, fp8_block=fp8_block)
     if synthetic:
         from .config import named_config
         from .weights import synthetic_weights
@@ -114,7 +116,7 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
                   repeat_prompt=0, stop_repetition=3, sample_batch_size=1, seed=1, output_dir="./generated_tts",
                   cut_off_sec=100, dump_tokens=False, lang=None, codec_dir=None, tokenizer_dir=None, synthetic=None,
                   codec="44k", device="cuda:0", whisper_model="large-v3-turbo", model=None, audio_tokenizer=None,
-                  text_tokenizer=None, asr_model=None, parity=True, weight_format="bf16"):
+                  text_tokenizer=None, asr_model=None, parity=True, weight_format="bf16", fp8_block=False):
     """inference_commandline_hf.py:72-242. ``model`` / ``audio_tokenizer`` /
     ``text_tokenizer`` / ``asr_model`` may be passed pre-built (then nothing is loaded).
     ``parity`` (default True, ``--parity False`` on the command line): reproduce the
@@ -124,10 +126,15 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
     step's weights to FP8 e4m3 with power-of-two row scales when the model is loaded (DESIGN.md
     §5 "FP8 mode"); it is fast path only, so the run is made with ``parity=False``. An unknown
     value raises ValueError before anything is loaded.
+    ``fp8_block`` (default False, ``--fp8_block True``): with ``weight_format="fp8"``, run the
+    whole-layer decode launch on the FP8 weights (engine ``set_fp8_block``); a ValueError with
+    any other format.
     Returns the path of the written wav."""
     from .weights import WEIGHT_FORMATS
     if weight_format not in WEIGHT_FORMATS:
         raise ValueError(f"weight_format {weight_format!r}: one of {WEIGHT_FORMATS}")
+    if fp8_block and weight_format != "fp8":
+        raise ValueError("fp8_block needs weight_format 'fp8' (--weight_format fp8)")
     if weight_format == "fp8" and parity:
         print("[Info] weight_format fp8 is fast path only: running with parity=False")
         parity = False
@@ -137,7 +144,7 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
 
     seed_everything(seed)
     if model is None:
-        model = load_model(model_dir, synthetic, device, weight_format=weight_format)
+        model = load_model(model_dir, synthetic, device, weight_format=weight_format, fp8_block=bool(fp8_block))
     cfg = model.config
     if text_tokenizer is None:
         if synthetic and _none(tokenizer_dir):
@@ -242,6 +249,8 @@ def main(argv=None) -> None:
             continue
         ap.add_argument(f"--{name}", type=str if name in _STR_ARGS else _arg, default=p.default)
     args = ap.parse_args(argv)
+    if args.fp8_block and args.weight_format != "fp8":
+        ap.error("--fp8_block needs --weight_format fp8")
     run_inference(**vars(args))
 
 

@@ -826,6 +826,7 @@ extern "C" int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* 
     }
     drop_graphs(e);   // captured steps hold the other format's launches
     e->fp8 = w != nullptr;
+    if (!w) e->fp8_block = false;   // the switch belongs to FP8 mode
     e->dec8.clear();
     e->head2_8 = {nullptr, nullptr};
     if (w) {
@@ -838,6 +839,16 @@ extern "C" int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* 
 extern "C" int t5g_engine_weight_format(t5g_engine* e, int32_t* fmt) {
     if (!e || !fmt) return T5G_EINVAL;
     *fmt = e->fp8 ? 1 : 0;
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_set_fp8_block(t5g_engine* e, int32_t enable) {
+    if (!e) return T5G_EINVAL;
+    if (enable && !e->fp8) return T5G_EUNSUPPORTED;
+    if (e->fp8_block != (enable != 0)) {
+        e->fp8_block = enable != 0;
+        drop_graphs(e);   // captured launches follow the flag
+    }
     return T5G_OK;
 }
 
@@ -1056,6 +1067,11 @@ FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
     return fa;
 }
 
+static void p8_weight(const bf16_t*& W, const float*& S, const t5g_fp8_linear& x) {
+    W = (const bf16_t*)x.p8;
+    S = x.scale;
+}
+
 // the same launch with the cross-attention chain in front (fused.hip fused_block_kernel):
 // o-proj slabs in e->part -> ... -> down slabs in e->part
 FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
@@ -1097,6 +1113,18 @@ FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
     fa.att_self = e->datt;
     fa.Wo1 = (const bf16_t*)L.o;
     fa.o1slab = fa.dslab + (size_t)8 * M * c.hidden;
+    // FP8 mode with the whole-layer launch on (t5g_engine_set_fp8_block): every weight of the
+    // launch is the Linear's P8 image with its row scales (fused_p8.hip; no mixed launch)
+    if (e->fp8 && e->fp8_block) {
+        const t5g_fp8_layer& P = e->dec8[l];
+        fa.wfmt = 1;
+        p8_weight(fa.Wo1, fa.sWo1, P.o);
+        p8_weight(fa.Wq, fa.sWq, P.cross_q);
+        p8_weight(fa.Wo, fa.sWo, P.cross_o);
+        p8_weight(fa.Wgu, fa.sWgu, P.gate_up);
+        p8_weight(fa.Wd, fa.sWd, P.down);
+        if (!last) p8_weight(fa.Wqkv, fa.sWqkv, e->dec8[l + 1].qkv);
+    }
     return fa;
 }
 
@@ -1124,11 +1152,13 @@ static void fused_s_fields(t5g_engine* e, int l, FusedMlpArgs& fa) {
 bool fused_block_tail(t5g_engine* e, int l, FusedMlpArgs& fa) {
     const t5g_config& c = e->c;
     fa.Wo1 = nullptr;   // the o-projection of this layer ran at the end of the previous launch
+    fa.sWo1 = nullptr;
     fa.o_slabs = l == 0 ? e->part : fa.o1slab;
     if (l == c.n_dec_layers - 1) return fused_mlp_check(fa) == 0;
     fused_s_fields(e, l + 1, fa);
     fa.self_tail = 1;
     fa.Wo1n = (const bf16_t*)e->dec[l + 1].o;
+    if (fa.wfmt) p8_weight(fa.Wo1n, fa.sWo1n, e->dec8[l + 1].o);
     fa.o1n = fa.o1slab;
     fa.att_self = e->datt;
     return fused_mlp_check(fa) == 0;
@@ -1166,9 +1196,14 @@ DecodePlan decode_plan(t5g_engine* e, int M, int block_rows, bool switches) {
     p.gate_up = rows32 && wd ? GemvSite{12, 1, -1, true} : M <= 16 ? GemvSite{8, 1, 8, false} : gemm_only;
     p.mlp_half = e->fused_mlp && rows32 && wd && wf && c.n_dec_layers >= 2;
     p.block = M <= block_rows && (!switches || (p.mlp_half && wq));
+    // FP8 mode: the whole-layer launch has a P8 form for one tile only, behind its own switch
+    // (t5g_engine_set_fp8_block; block_rows above 16 does not apply); the MLP-half launch has
+    // none. Everything else runs the per-op launches on the P8 GEMVs.
+    if (e->fp8) {
+        p.block = p.block && e->fp8_block && M <= 16;
+        p.mlp_half = false;
+    }
     // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
-    // FP8 mode: per-op launches at every batch size (the persistent launches stream bf16 only)
-    if (e->fp8) p.mlp_half = p.block = false;
     p.tail = p.block && e->attn_in_block == 2 && (!switches || e->attn_flash);
     for (int l = 0; l < c.n_dec_layers && p.tail; ++l) {
         FusedMlpArgs fa = fused_block_args(e, M, l);
@@ -1365,7 +1400,7 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
             // o-projection at its end (bitwise equal to the launches below)
             if (l == 0) {
                 RC(self_attention(l));
-                RC(out_proj(L.o, nullptr));
+                RC(out_proj(L.o, L8 ? &L8->o : nullptr));
             }
             fa = fused_block_args(e, M, l);
             if (!fused_block_tail(e, l, fa)) return T5G_EUNSUPPORTED;   // the plan checked every layer

@@ -169,7 +169,7 @@ extern "C" int t5g_time_xlayer(t5g_engine* e, int32_t B, int32_t iters, void* st
 // launch streams its weights from HBM (2.2 GB of gate/up + down > the 256 MiB Infinity Cache)
 extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
     if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
-    if (e->fp8) return T5G_EUNSUPPORTED;   // the persistent launches stream bf16 weights only
+    if (e->fp8) return T5G_EUNSUPPORTED;   // the MLP-half launch streams bf16 weights only
     e->decode_state_invalid = true;
     hipStream_t st = (hipStream_t)stream;
     const int L = e->c.n_dec_layers;
@@ -200,7 +200,8 @@ extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void
 extern "C" int t5g_time_decode_layer(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us,
                                      float* keys) {
     if (!e || iters <= 0 || !avg_us || !keys || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
-    if (e->fp8) return T5G_EUNSUPPORTED;   // the persistent launches stream bf16 weights only
+    // FP8 mode: only with t5g_engine_set_fp8_block on (the plan below then refuses > 16 rows)
+    if (e->fp8 && !e->fp8_block) return T5G_EUNSUPPORTED;
     e->decode_state_invalid = true;
     hipStream_t st = (hipStream_t)stream;
     const t5g_config& c = e->c;
@@ -245,9 +246,11 @@ extern "C" int t5g_time_decode_layer(t5g_engine* e, int32_t B, int32_t iters, vo
         if (!args(i % L, fa)) return T5G_EUNSUPPORTED;
         if (share == 1 && i % L != L - 1) {
             fa.Wq = f1.Wq, fa.Wo = f1.Wo, fa.Wqkv = f1.Wqkv, fa.ck = f1.ck, fa.cv = f1.cv;
-            if (fa.Wo1n) fa.Wo1n = f1.Wo1n;
+            fa.sWq = f1.sWq, fa.sWo = f1.sWo, fa.sWqkv = f1.sWqkv;   // (P8: a weight's scales go with it)
+            if (fa.Wo1n) fa.Wo1n = f1.Wo1n, fa.sWo1n = f1.sWo1n;
         } else if (share == 2) {
             fa.Wgu = f1.Wgu, fa.Wd = f1.Wd;
+            fa.sWgu = f1.sWgu, fa.sWd = f1.sWd;
         }
         return launch_rc(fused_mlp(fa, st));
     };

@@ -141,9 +141,11 @@ struct t5g_engine {
     int64_t xl_launches = 0;   // xlayer.hip launches issued (captured ones counted once, at capture)
     // FP8 mode (t5g_engine_set_fp8_weights): the P8 images + row scales of the decode step's
     // Linears; the P16 pointers above are then the images of the same W_q. The fast decode
-    // step runs its register-X GEMV sites and the head on them (per-op launches at every
-    // batch size: the persistent launches stream bf16 weights only)
+    // step runs its register-X GEMV sites and the head on them: per-op launches at every
+    // batch size, unless fp8_block (t5g_engine_set_fp8_block) lets 1-16 rows take the
+    // whole-layer launch on the P8 images (fused_p8.hip)
     bool fp8 = false;
+    bool fp8_block = false;
     std::vector<t5g_fp8_layer> dec8;
     t5g_fp8_linear head2_8 = {nullptr, nullptr};
 };

@@ -28,8 +28,16 @@
 // Numerics: every stage is the exact arithmetic of the kernels it replaces (the same
 // per-wave k-step chains, the same fixed-order wave reductions, the same norm reductions),
 // so the fused launch is bitwise equal to the three launches (tests/test_gpu_fused.py).
+//
+// Weight formats: fused_mlp_kernel and the two-tile fused_block_kernel stream bf16 (P16)
+// weights only. The one-tile fused_block_kernel also has a P8 form (FP8 e4m3 codes + row
+// scales, fp8.h; fused_p8.hip, FusedMlpArgs::wfmt = 1, opt-in through
+// t5g_engine_set_fp8_block): all seven weights of a launch as P8 images, 8-byte requests in
+// the places of the 16-byte ones, each fragment converted in front of its MFMA -- bitwise
+// the bf16 kernel on the dequantised weights (tests/test_gpu_fp8_block.py).
 #include "common.h"
 #include "attn_chunk.h"
+#include "fp8.h"
 #include "t5g_kernels.h"
 
 namespace t5g {
@@ -38,10 +46,19 @@ namespace t5g {
 // unit of their own (fused_rows32.hip includes this file with T5G_FUSED_ROWS32 defined):
 // instantiated beside the one-tile kernels they change the compiler's inlining decisions for
 // those, and the one-tile kernels stay the code they were.
-#ifdef T5G_FUSED_ROWS32
+//
+// The FP8 (P8, fp8.h) instantiations of the one-tile kernels are a third translation unit for
+// the same reason (fused_p8.hip, T5G_FUSED_P8). Both secondary units define
+// T5G_FUSED_SECONDARY: they carry kernels only, the launcher and the diagnostic symbols stay here.
+#if defined(T5G_FUSED_ROWS32)
 T5G_TS_UNIT(fused_rows32)
+#elif defined(T5G_FUSED_P8)
+T5G_TS_UNIT(fused_p8)
 #else
 T5G_TS_UNIT(fused)
+#endif
+#if defined(T5G_FUSED_ROWS32) || defined(T5G_FUSED_P8)
+#define T5G_FUSED_SECONDARY 1
 #endif
 
 constexpr int FM_NW = 12;         // waves per workgroup (the gate/up and down kernels' count)
@@ -405,21 +422,65 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
 // followed by that layer's O1 into the slabs the next launch's N1 reads
 // (tests/test_gpu_attn_in_block.py: bitwise equal to the separate flash launch).
 
+// Weight format of the block kernel's GEMV stages (WF): P16 bf16 fragments, or P8 (fp8.h) --
+// e4m3 codes in the same lane order, 8 bytes per lane and k-step, plus the lane's fp32 row
+// scale per unit; p8_to_bf16 in front of each MFMA gives exactly the P16 fragment of the
+// dequantised weights W_q, so a P8 stage is bitwise the P16 stage on W_q. A stage's weight
+// registers FbW<WF, UMAX, SPU>: P16 the plain fragment array the kernels always had, P8 half
+// as many registers for the codes plus one scale per unit.
+constexpr int WF_P16 = 0, WF_P8 = 1;
+template <int UMAX, int SPU>
+struct FbW8 {
+    u32x2 w[UMAX][SPU];
+    float s[UMAX];
+};
+template <int WF, int UMAX, int SPU>
+struct FbWT {
+    typedef bf16x8_s type[UMAX][SPU];
+};
+template <int UMAX, int SPU>
+struct FbWT<WF_P8, UMAX, SPU> {
+    typedef FbW8<UMAX, SPU> type;
+};
+template <int WF, int UMAX, int SPU>
+using FbW = typename FbWT<WF, UMAX, SPU>::type;
+
 // Split form of fm_gemv: the weight requests (waves < NWG) ...
-template <int NWG, int SPU, int UMAX>
-__device__ __forceinline__ void fb_issue(bf16x8_s (&w)[UMAX][SPU], const bf16_t* W, int NG, int KB, int kb_lo, int KBs,
-                                         int g0, int gs, int nu) {
+// P8 (S: the row scales): the same (unit, k-step) requests, 8 bytes each. NG is also the
+// image's group count (every width here is a multiple of 16: the launcher checks it), so the
+// descriptor ends with the image as gemv_rx_kernel<.., P8>'s does and a P16 padding group
+// reads zero codes. The lane's row scale once per unit, unconditionally: past the image it
+// reads 0, on zero codes.
+template <int NWG, int SPU, int UMAX, int WF = WF_P16>
+__device__ __forceinline__ void fb_issue(FbW<WF, UMAX, SPU>& w, const bf16_t* W, const float* S, int NG, int KB,
+                                         int kb_lo, int KBs, int g0, int gs, int nu) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave >= NWG) return;
-    const __amdgpu_buffer_rsrc_t wr = frag_rsrc(W, (uint32_t)NG * (uint32_t)KB * 1024u);
+    if constexpr (WF == WF_P8) {
+        const __amdgpu_buffer_rsrc_t wr = frag_rsrc(W, (uint32_t)NG * (uint32_t)KB * 512u);
+        const __amdgpu_buffer_rsrc_t sr = frag_rsrc(S, (uint32_t)NG * 64u);
 #pragma unroll
-    for (int i = 0; i < UMAX; ++i) {
-        const int g = g0 + i * gs;
+        for (int i = 0; i < UMAX; ++i) {
+            const int g = g0 + i * gs;
 #pragma unroll
-        for (int j = 0; j < SPU; ++j) {
-            const int kb = wave + j * NWG;
-            const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 16 : (int)0xfffffff0u;
-            w[i][j] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, AUX_NT));
+            for (int j = 0; j < SPU; ++j) {
+                const int kb = wave + j * NWG;
+                const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 8 : (int)0xfffffff0u;
+                w.w[i][j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(wr, off, 0, AUX_NT));
+            }
+            w.s[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(sr, (g * 16 + (lane & 15)) * 4, 0, 0));
+        }
+    } else {
+        const __amdgpu_buffer_rsrc_t wr = frag_rsrc(W, (uint32_t)NG * (uint32_t)KB * 1024u);
+#pragma unroll
+        for (int i = 0; i < UMAX; ++i) {
+            const int g = g0 + i * gs;
+#pragma unroll
+            for (int j = 0; j < SPU; ++j) {
+                const int kb = wave + j * NWG;
+                const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 16 : (int)0xfffffff0u;
+                w[i][j] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, AUX_NT));
+            }
         }
     }
 }
@@ -438,11 +499,18 @@ __device__ __forceinline__ void fb_issue(bf16x8_s (&w)[UMAX][SPU], const bf16_t*
 struct FbNoMid {
     __device__ __forceinline__ bool operator()() const { return false; }
 };
-template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false, int MT = 1, typename Mid = FbNoMid>
-__device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int gs, int nu, int kb_lo, int KBs,
-                                          const bf16_t* X, int ldx, int xbytes, int M, void* Y, int ldy, int ybytes,
-                                          int N, f32x4* red, const char* lw = nullptr, int nu_reg = 0, Mid mid = Mid()) {
+//
+// WF = P8: each fragment is converted with its unit's row scale (w.s) directly in front of the
+// MFMA that takes it -- the MFMA operands are the P16 fragments of W_q in the same order, and
+// nothing else differs. The LDS unit is the P8 image too (512 B per k-step, lane-linear: 8
+// bytes per lane), converted with w.s[nu_reg], the scale fb_issue loaded for that unit.
+template <int NWG, int EPI, int SPU, int UMAX, int OUT, bool LDSU = false, int MT = 1, int WF = WF_P16,
+          typename Mid = FbNoMid>
+__device__ __forceinline__ void fb_finish(FbW<WF, UMAX, SPU>& w, int g0, int gs, int nu, int kb_lo, int KBs, const bf16_t* X, int ldx, int xbytes, int M, void* Y,
+                                          int ldy, int ybytes, int N, f32x4* red, const char* lw = nullptr,
+                                          int nu_reg = 0, Mid mid = Mid()) {
     static_assert(MT == 1 || (!LDSU && EPI != EPI_GEGLU), "the LDS unit and the GeGLU epilogue are one-tile only");
+    static_assert(WF == WF_P16 || MT == 1, "P8 weights: one tile");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int xr = lane & 15;
     wg_barrier();   // the hand-off is complete (or abandoned) for every wave past here
@@ -468,16 +536,28 @@ __device__ __forceinline__ void fb_finish(bf16x8_s (&w)[UMAX][SPU], int g0, int 
             for (int i = 0; i < UMAX; ++i) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < SPU; ++j) acc = mfma16(w[i][j], xf[j], acc);
+                for (int j = 0; j < SPU; ++j) {
+                    if constexpr (WF == WF_P8) acc = mfma16(p8_to_bf16(w.w[i][j], w.s[i]), xf[j], acc);
+                    else acc = mfma16(w[i][j], xf[j], acc);
+                }
                 if (i < nr) red[((i * MT + t) * NWG + wave) * 64 + lane] = acc;
             }
         }
         if constexpr (LDSU) {   // (one tile)
             if (nu_reg < nu) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (WF == WF_P8) {
+                    float sl = 0.f;   // w.s[nu_reg] without a register-array index
+#pragma unroll
+                    for (int i = 0; i < UMAX; ++i) sl = i == nu_reg ? w.s[i] : sl;
+#pragma unroll
+                    for (int j = 0; j < SPU; ++j)
+                        acc = mfma16(p8_to_bf16(*(const u32x2*)(lw + ((wave + j * NWG) * 64 + lane) * 8), sl), xf[j], acc);
+                } else {
 #pragma unroll
                 for (int j = 0; j < SPU; ++j)
                     acc = mfma16(*(const bf16x8_s*)(lw + ((wave + j * NWG) * 64 + lane) * 16), xf[j], acc);
+                }
                 red[(nu_reg * NWG + wave) * 64 + lane] = acc;
             }
         }
@@ -634,7 +714,7 @@ static_assert(sizeof(FbSelfLds) <= 5 * FM_NW * 1024, "stage S lives in the GEMV 
 // diagnostic timeline of stage S and O1 (T5G_DBG_TS library variant only,
 // tools/diag_fused_s.py): thread 0 (or `tid`) of every workgroup stores the 100 MHz clock at
 // numbered points, 32 slots per workgroup
-#if defined(T5G_DBG_TS) && !defined(T5G_FUSED_ROWS32)
+#if defined(T5G_DBG_TS) && !defined(T5G_FUSED_SECONDARY)
 __device__ unsigned long long* fs_ts_buf;
 extern "C" int t5g_dbg_set_fused_s(void* p) {
     return hipMemcpyToSymbol(HIP_SYMBOL(fs_ts_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
@@ -1034,12 +1114,21 @@ __device__ __forceinline__ void fb_self_attn(const FusedMlpArgs& a, FbSelfLds& s
 //               the tail's stage S scratch lives in `red` (free between the q|k|v hand-off
 //               and the next layer's O1)
 //
-// One template parameter V = SM + 4 (MT - 1), so the one-tile kernels keep their names
-// (fused_block_kernel<0..2>; the profiles and tools/ name them) and their code.
+// WF: the weight format of every GEMV stage of the launch (all seven weights; no mixed mode).
+// WF = P8 (one tile only, fused_p8.hip) streams half the bytes per request and holds half the
+// weight registers per stage; the requests (which wave asks for which (unit, k-step), and when:
+// O's around the attention, gate/up's with the LDS copies, down's under gate/up's epilogue),
+// the hand-offs and every sum are the P16 kernel's. The gate/up unit in LDS is 36 KiB of the
+// 72 KiB region; the tail's stage-S scratch keeps its place in that region.
+//
+// One template parameter V = SM + 4 (MT - 1) + 8 WF, so the bf16 one-tile kernels keep their
+// names (fused_block_kernel<0..2>; the profiles and tools/ name them) and their code; the P8
+// kernels are fused_block_kernel<8..10>.
 template <int V>
 __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a) {
-    constexpr int SM = V & 3, MT = 1 + (V >> 2);
+    constexpr int SM = V & 3, MT = 1 + ((V >> 2) & 1), WF = V >> 3;
     static_assert(SM <= 2 && (MT == 1 || MT == 2), "S placement 0-2, one or two 16-row tiles");
+    static_assert(WF == WF_P16 || (WF == WF_P8 && MT == 1), "P8 weights: the one-tile kernels only");
     constexpr bool SELF = SM == 1;
     constexpr int RED_B = 5 * MT * FM_NW * 1024;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1238,11 +1327,11 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     // each (<= 3 units, 8 waves); its input is the previous launch's (no wait), or stage S's:
     // k-slice so is the q-head pair of kv head so, complete when its M rows have published
     if (a.Wo1 && owork) {
-        bf16x8_s w1[3][2];
-        fb_issue<8, 2, 3>(w1, a.Wo1, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+        FbW<WF, 3, 2> w1;
+        fb_issue<8, 2, 3, WF>(w1, a.Wo1, a.sWo1, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
         if (SELF && wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_S0 + so, (unsigned)M, tmo, 17u);
         if constexpr (SELF) FS_TS_BY(9, (FM_NW - 1) * 64);
-        fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
+        fb_finish<8, EPI_F32, 2, 3, 2, false, MT, WF>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
                                        a.o1slab + (long)so * M * d, d, M * d * 4, d, red);
         fb_publish(cline(a.sync, L_P0 + (w & 7)), 1u);
         if constexpr (SELF) FS_TS(10);
@@ -1254,15 +1343,15 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         const int qper = nw / 2, sq = w / qper, jq = w - sq * qper;
         if (sq < 2) {
             const int nu_q = (a.NGq - jq + qper - 1) / qper;
-            bf16x8_s wq[2][3];
+            FbW<WF, 2, 3> wq;
             // every wave's weights first, the poller's too: they were requested ~5 us before
             // N1 completes, so its poll is not held back by them, and wave 0's share no
             // longer starts only when the hand-off is seen
-            fb_issue<FM_NW, 3, 2>(wq, a.Wq, a.NGq, d / 32, sq * 36, 36, jq, qper, nu_q);
+            fb_issue<FM_NW, 3, 2, WF>(wq, a.Wq, a.sWq, a.NGq, d / 32, sq * 36, 36, jq, qper, nu_q);
             if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N1, (unsigned)M, tmo, 1u);
             T5G_TS(1);
             if constexpr (SELF) FS_TS(11);
-            fb_finish<FM_NW, EPI_F32, 3, 2, 2, false, MT>(wq, jq, qper, nu_q, sq * 36, 36, a.xn1, d, M * d * 2, M,
+            fb_finish<FM_NW, EPI_F32, 3, 2, 2, false, MT, WF>(wq, jq, qper, nu_q, sq * 36, 36, a.xn1, d, M * d * 2, M,
                                                a.qslab + (long)sq * M * a.q_dim, a.q_dim, M * a.q_dim * 4, a.q_dim,
                                                red);
             drain_vm();
@@ -1285,12 +1374,26 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     // entry. g_early is a scalar, so both sides are real branches: these waves cross O on its
     // barriers alone (O's code with wg live is never theirs), and O's publish drains their
     // requests with the LDS copies. Wave 11 polls in O and requests nothing early.
-    bf16x8_s wg[5][6];
+    //
+    // P8: the unit is 72 k-steps x 512 B = 36 KiB. LDS-DMA has no 8-byte width, so the copies
+    // stay 16 bytes per lane: one instruction moves 1 KiB = two consecutive k-step fragments,
+    // 12 per wave. The image is lane-linear, so LDS holds the P8 unit byte for byte (k-step kb
+    // at kb x 512, lane l's 8 codes at + 8 l), in the first half of the region.
+    FbW<WF, 5, 6> wg;
     const int nu_r = gu_lds ? nu_g - 1 : nu_g;
     const int swave = __builtin_amdgcn_readfirstlane(wave);
     const bool g_early = MT == 1 && gu_lds && swave >= 8 && swave < 11;
     if (gu_lds && wave >= 8 && wave < 11) {
         const int wv = __builtin_amdgcn_readfirstlane(wave - 8);
+        if constexpr (WF == WF_P8) {
+            constexpr int PER = FB_GU_KB / 2 / 3;   // 1 KiB copies per wave
+            const __amdgpu_buffer_rsrc_t gr = frag_rsrc(a.Wgu, (uint32_t)NGg * (uint32_t)KBg * 512u);
+            const int gb = (g_lo + nu_g - 1) * KBg * 512 + wv * PER * 1024 + lane * 16;
+            __attribute__((address_space(3))) char* dst = (__attribute__((address_space(3))) char*)gul + wv * PER * 1024;
+#pragma unroll
+            for (int q = 0; q < PER; ++q)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(gr, dst + q * 1024, 16, gb + q * 1024, 0, 0, AUX_NT);
+        } else {
         const __amdgpu_buffer_rsrc_t gr = frag_rsrc(a.Wgu, (uint32_t)NGg * (uint32_t)KBg * 1024u);
         const int gb = ((g_lo + nu_g - 1) * KBg + wv * (FB_GU_KB / 3)) * 1024 + lane * 16;
         __attribute__((address_space(3))) char* dst =
@@ -1298,9 +1401,10 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
 #pragma unroll
         for (int q = 0; q < FB_GU_KB / 3; ++q)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(gr, dst + q * 1024, 16, gb + q * 1024, 0, 0, AUX_NT);
+        }
     }
     if (g_early) {
-        fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
+        fb_issue<FM_NW, 6, 5, WF>(wg, a.Wgu, a.sWgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
         if (owork) {          // O's rendezvous for a wave with no part in it:
             wg_barrier();     // fb_finish's hand-off barrier,
             __syncthreads();  // the barrier that closes its MFMA part,
@@ -1310,8 +1414,8 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     } else {
         // ---- A (attention workers) with O's weight requests around it
         // (two tiles: waves 4-7 run the pair's second head, so O's requests follow the attention)
-        bf16x8_s wo[3][2];
-        if (MT == 1 && attnwg && wave >= 4 && owork) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+        FbW<WF, 3, 2> wo;
+        if (MT == 1 && attnwg && wave >= 4 && owork) fb_issue<8, 2, 3, WF>(wo, a.Wo, a.sWo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
         if (attnwg) {
             const int qcnt = 2 * (D / 16);   // 16 q units per head x 2 k-slices
             // (wave 0's head is the pair's first: two tiles poll both heads' lines at once)
@@ -1424,10 +1528,10 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         if (owork) {
             // waves 0-7 (the GEMV) request their weights first; wave 11, idle in this stage and
             // with nothing queued, polls the 8 q heads
-            if (!(MT == 1 && attnwg && wave >= 4)) fb_issue<8, 2, 3>(wo, a.Wo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+            if (!(MT == 1 && attnwg && wave >= 4)) fb_issue<8, 2, 3, WF>(wo, a.Wo, a.sWo, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
             if (wave == FM_NW - 1) ok &= fm_wait_n<8>(a.sync, L_A0, (unsigned)M, tmo, 3u);
             T5G_TS_BY(2, (FM_NW - 1) * 64);
-            fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
+            fb_finish<8, EPI_F32, 2, 3, 2, false, MT, WF>(wo, jo, oper, nu_o, so * 16, 16, a.att, a.q_dim, M * a.q_dim * 2, M,
                                            a.oslab + (long)so * M * d, d, M * d * 4, d, red);
             fb_publish(cline(a.sync, L_O0 + (w & 7)), 1u);
         }
@@ -1441,19 +1545,19 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     // waves' epilogue, drain and publish. Only the storing waves drain, and the barrier in front
     // of the publish is the raw one: the early requests stay in flight across it. wg is dead by
     // then, so no two weight arrays are live in any MFMA.
-    bf16x8_s wd[5][3];
+    FbW<WF, 5, 3> wd;
     bool d_early = false;
     if constexpr (MT == 1) {
-        if (!g_early) fb_issue<FM_NW, 6, 5>(wg, a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
+        if (!g_early) fb_issue<FM_NW, 6, 5, WF>(wg, a.Wgu, a.sWgu, NGg, KBg, 0, KBg, g_lo, 1, nu_r);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u);
         T5G_TS(3);
         const int dper = nw / FM_DS, s = w / dper, j = w - s * dper;   // D's mapping (below)
         d_early = s < FM_DS && __builtin_amdgcn_readfirstlane(wave) >= nu_g;
-        fb_finish<FM_NW, EPI_GEGLU, 6, 5, 0, true>(wg, g_lo, 1, nu_g, 0, KBg, a.xn, d, M * d * 2, M, a.act, f,
+        fb_finish<FM_NW, EPI_GEGLU, 6, 5, 0, true, 1, WF>(wg, g_lo, 1, nu_g, 0, KBg, a.xn, d, M * d * 2, M, a.act, f,
                                                    M * f * 2, 2 * f, red, gul, nu_r, [&]() {
                                                        if (!d_early) return false;
                                                        const int KBd = f / 32, per = KBd / FM_DS;
-                                                       fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper,
+                                                       fb_issue<FM_NW, 3, 5, WF>(wd, a.Wd, a.sWd, a.NGd, KBd, s * per, per, j, dper,
                                                                              (a.NGd - j + dper - 1) / dper);
                                                        return true;
                                                    });
@@ -1487,10 +1591,10 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
     if (s < FM_DS) {
         const int KBd = f / 32, per = KBd / FM_DS;
         const int nu_d = (a.NGd - j + dper - 1) / dper;
-        if (!d_early) fb_issue<FM_NW, 3, 5>(wd, a.Wd, a.NGd, KBd, s * per, per, j, dper, nu_d);
+        if (!d_early) fb_issue<FM_NW, 3, 5, WF>(wd, a.Wd, a.sWd, a.NGd, KBd, s * per, per, j, dper, nu_d);
         if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_SL0 + s, (unsigned)units_per_slice, tmo, 6u + s);
         T5G_TS(5);
-        fb_finish<FM_NW, EPI_F32, 3, 5, 2, false, MT>(wd, j, dper, nu_d, s * per, per, a.act, f, M * f * 2, M,
+        fb_finish<FM_NW, EPI_F32, 3, 5, 2, false, MT, WF>(wd, j, dper, nu_d, s * per, per, a.act, f, M * f * 2, M,
                                            a.dslab + (long)s * M * d, d, M * d * 4, d, red);
         fb_publish(cline(a.sync, L_D0 + (w & 7)), 1u);
     }
@@ -1503,14 +1607,14 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             // the tail: q|k|v written through and handed off in-launch, the next layer's self
             // attention (its K / V requested before the N3 wait), then the next layer's O1
             const int nu_k = sk < 2 ? (a.NGqkv - jk + kper - 1) / kper : 0;
-            bf16x8_s wk[3][3];
-            fb_issue<FM_NW, 3, 3>(wk, a.Wqkv, a.NGqkv, d / 32, sk * 36, 36, jk, kper, nu_k);
+            FbW<WF, 3, 3> wk;
+            fb_issue<FM_NW, 3, 3, WF>(wk, a.Wqkv, a.sWqkv, a.NGqkv, d / 32, sk * 36, 36, jk, kper, nu_k);
             auto mid = [&]() __attribute__((always_inline)) {
                 // wave 11 (group 2: never a chunk slot in the tail, so no K / V queued ahead of
                 // its polls) waits for N3, then for every q|k|v workgroup
                 if (wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_N3, (unsigned)M, tmo, 15u);
                 FS_TS_BY(17, (FM_NW - 1) * 64);
-                fb_finish<FM_NW, EPI_F32, 3, 3, 2, false, MT>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
+                fb_finish<FM_NW, EPI_F32, 3, 3, 2, false, MT, WF>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
                                                    a.qkv_out + (long)sk * M * a.qkv_dim, a.qkv_dim,
                                                    M * a.qkv_dim * 4, a.qkv_dim, red);
                 fb_publish(cline(a.sync, L_K0 + (w & 7)), 1u);   // every worker (an odd one projects nothing)
@@ -1530,20 +1634,20 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
             }
             // the next layer's O1: k-slice so waits for kv head so's rows
             if (owork) {
-                bf16x8_s w1[3][2];
-                fb_issue<8, 2, 3>(w1, a.Wo1n, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
+                FbW<WF, 3, 2> w1;
+                fb_issue<8, 2, 3, WF>(w1, a.Wo1n, a.sWo1n, a.NGo, a.q_dim / 32, so * 16, 16, jo, oper, nu_o);
                 if (wave == FM_NW - 1) ok &= fm_wait_n<1>(a.sync, L_S0 + so, (unsigned)M, tmo, 20u);
                 FS_TS_BY(20, (FM_NW - 1) * 64);
-                fb_finish<8, EPI_F32, 2, 3, 2, false, MT>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
+                fb_finish<8, EPI_F32, 2, 3, 2, false, MT, WF>(w1, jo, oper, nu_o, so * 16, 16, a.att_self, a.q_dim, M * a.q_dim * 2, M,
                                                a.o1n + (long)so * M * d, d, M * d * 4, d, red);
                 FS_TS(21);
             }
         } else if (sk < 2) {
             const int nu_k = (a.NGqkv - jk + kper - 1) / kper;
-            bf16x8_s wk[3][3];
-            fb_issue<FM_NW, 3, 3>(wk, a.Wqkv, a.NGqkv, d / 32, sk * 36, 36, jk, kper, nu_k);
+            FbW<WF, 3, 3> wk;
+            fb_issue<FM_NW, 3, 3, WF>(wk, a.Wqkv, a.sWqkv, a.NGqkv, d / 32, sk * 36, 36, jk, kper, nu_k);
             if (wave == 0) ok &= fm_wait_n<1>(a.sync, L_N3, (unsigned)M, tmo, 15u);
-            fb_finish<FM_NW, EPI_F32, 3, 3, 1, false, MT>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
+            fb_finish<FM_NW, EPI_F32, 3, 3, 1, false, MT, WF>(wk, jk, kper, nu_k, sk * 36, 36, a.xn, d, M * d * 2, M,
                                                a.qkv_out + (long)sk * M * a.qkv_dim, a.qkv_dim, 0, a.qkv_dim, red);
         }
     }
@@ -1552,13 +1656,19 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
 }
 
 typedef void (*fused_block_fn)(FusedMlpArgs);
-#ifdef T5G_FUSED_ROWS32
+#if defined(T5G_FUSED_ROWS32)
 // the two-tile kernel for stage S placement sv (0 none, 1 in front, 2 the tail)
 fused_block_fn fused_block_rows32_kernel(int sv) {
     return sv == 2 ? fused_block_kernel<6> : sv ? fused_block_kernel<5> : fused_block_kernel<4>;
 }
+#elif defined(T5G_FUSED_P8)
+// the one-tile P8 kernel for stage S placement sv
+fused_block_fn fused_block_p8_kernel(int sv) {
+    return sv == 2 ? fused_block_kernel<10> : sv ? fused_block_kernel<9> : fused_block_kernel<8>;
+}
 #else
 fused_block_fn fused_block_rows32_kernel(int sv);   // fused_rows32.hip
+fused_block_fn fused_block_p8_kernel(int sv);       // fused_p8.hip
 
 constexpr size_t FM_LDS_MAX = 160 * 1024;
 
@@ -1576,6 +1686,12 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
         !a.sync_next || !a.timeout || a.sync_next == a.sync)
         return -1;
     if (a.NGgu * 8 != a.f || a.NGd * 16 != a.d) return -1;
+    // P8 weights: the one-tile whole-layer kernels only (no MLP-half or two-tile form), every
+    // weight of the launch with its row scales
+    if (a.wfmt != 0 &&
+        (a.wfmt != 1 || a.M > 16 || !a.xattn || !a.sWgu || !a.sWd || !a.sWq || !a.sWo || (a.Wo1 && !a.sWo1) ||
+         (a.Wqkv && !a.sWqkv) || (a.self_tail && !a.sWo1n)))
+        return -1;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev))
         return -2;
@@ -1637,15 +1753,17 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
              a.M * a.Hkv * a.s_nsplit > 2 * nw || (long)a.M * a.Hkv * a.s_nsplit * FS_G * FS_D * 4 > 0x7fff0000L))
             return -1;
         const int sv = a.self_tail ? 2 : a.self_attn ? 1 : 0;
-        fused_block_fn fb = MT == 2 ? fused_block_rows32_kernel(sv)
+        const int fi = a.wfmt ? 2 : MT - 1;   // kernel family: one tile, two tiles, one tile P8
+        fused_block_fn fb = a.wfmt ? fused_block_p8_kernel(sv)
+                            : MT == 2 ? fused_block_rows32_kernel(sv)
                             : sv == 2 ? fused_block_kernel<2> : sv ? fused_block_kernel<1> : fused_block_kernel<0>;
-        static bool attr_b[64][2][3] = {};
-        if (!attr_b[dev][MT - 1][sv]) {
+        static bool attr_b[64][3][3] = {};
+        if (!attr_b[dev][fi][sv]) {
             (void)hipFuncSetAttribute((const void*)fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FM_LDS_MAX);
             int occ = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fb, FM_NW * 64, shm) != hipSuccess || occ < 1)
                 return -1;
-            attr_b[dev][MT - 1][sv] = true;
+            attr_b[dev][fi][sv] = true;
         }
         if (!launch) return 0;
         hipLaunchKernelGGL(fb, dim3((unsigned)nb), dim3(FM_NW * 64), shm, st, a);

@@ -4,12 +4,17 @@ tokens per row): one process, one session, the arms interleaved round after roun
     bf16          the default engine (whole-layer launches)
     fp8           weight_format="fp8" (per-op launches on the P8 GEMVs, P8 head)
     bf16_per_op   the default engine after set_fused(False): the same launches as fp8, on bf16
+    fp8_block     the fp8 engine after set_fp8_block(True): whole-layer launches on the P8 images
 
 each ``--steps`` timed generate() calls after ``--warmup`` untimed ones, as bench.py times
 them (the workload definitions are bench.py's own, imported). One JSON line per run goes to
-``--out`` (default profiles/r09_fp8_c3_ab.jsonl), then a summary line: tok/s per run, the
+``--out`` (default profiles/r12_fp8_block_c3_ab.jsonl), then a summary line: tok/s per run, the
 within-arm spread over the rounds, and the device time of one decode step (t5g_time_decode_step)
-per arm. The baseline of any statement about fp8 is the bf16 runs of the same file.
+per arm. The arms that take the whole-layer launch also record the launch alone
+(t5g_time_decode_layer: ``decode_layer_us`` with stage S where the step runs it,
+``decode_layer_front_us`` after set_attn_in_block(1)), the launch's algorithmic bytes in the
+arm's format (``_lib.fused_block_bytes``) and with them its fraction of the 8 TB/s HBM peak.
+The baseline of any statement about fp8 or fp8_block is the bf16 runs of the same file.
 
     python tools/bench_weight_format.py --rounds 2 --steps 20 --warmup 5
 """
@@ -33,7 +38,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="c3")
     ap.add_argument("--time-iters", type=int, default=200, help="decode steps timed by t5g_time_decode_step")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r09_fp8_c3_ab.jsonl"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r12_fp8_block_c3_ab.jsonl"))
     args = ap.parse_args()
 
     import torch
@@ -54,11 +59,30 @@ def main() -> None:
     rows = bench.request_rows(cfg, B, T_x, T_p)
     utts = [Utterance(x=r[3:3 + r[0]], y=r[3 + r[0]:], tgt_y_len=r[1]) for r in rows]
     params = SamplingParams(top_k=30, top_p=0.9, temperature=0.8, stop_repetition=3, eos_disabled=True)
-    arms = ["bf16", "fp8", "bf16_per_op"]
+    arms = ["bf16", "fp8", "bf16_per_op", "fp8_block"]
+    bb = cfg.backbone
+    shape = dict(d=bb.hidden_size, f=bb.intermediate_size, q_dim=bb.num_attention_heads * bb.head_dim,
+                 kv_dim=bb.num_key_value_heads * bb.head_dim, n_layers=bb.num_decoder_layers)
+
+    def layer_launch(eng, stream, mode: int) -> dict:
+        """The whole-layer launch alone (208 launches rotated over the layers, as bench.py's
+        roofline leg), with stage S placed by set_attn_in_block(mode)."""
+        us, keys = C.c_float(), C.c_float()
+        eng.set_attn_in_block(mode)
+        try:
+            _lib.check(eng.L.t5g_time_decode_layer(eng.h, B, 208, stream, C.byref(us), C.byref(keys)),
+                       "time_decode_layer")
+        finally:
+            eng.set_attn_in_block(2)
+        nbytes = _lib.fused_block_bytes(B, T_x, self_keys=keys.value, weight_format=eng.weight_format, **shape)
+        return {"us": round(us.value, 2), "keys": round(keys.value, 1), "bytes": round(nbytes),
+                "hbm_peak_fraction": round(nbytes / (us.value * 1e-6) / 8e12, 4)}
 
     def run(arm: str, rnd: int) -> dict:
-        eng = engines["fp8" if arm == "fp8" else "bf16"]
+        eng = engines["fp8" if arm.startswith("fp8") else "bf16"]
         eng.set_fused(arm != "bf16_per_op")
+        if eng.weight_format == "fp8":
+            eng.set_fp8_block(arm == "fp8_block")
         step = lambda i: sum(len(g) for g in eng.generate(   # noqa: E731
             utts, params, seeds=[bench.request_seed(i, r[2]) for r in rows], chunk=64)["gen"])
         for i in range(args.warmup):
@@ -72,8 +96,17 @@ def main() -> None:
         us = C.c_float()
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(eng.L.t5g_time_decode_step(eng.h, args.time_iters, stream, C.byref(us)), "time_decode_step")
+        out = {}
+        if arm in ("bf16", "fp8_block"):
+            tail, front = layer_launch(eng, stream, 2), layer_launch(eng, stream, 1)
+            out = {"decode_layer_us": tail["us"], "decode_layer_front_us": front["us"],
+                   "fused_block_bytes": tail["bytes"], "decode_layer_keys": tail["keys"],
+                   "decode_layer_hbm_peak_fraction": tail["hbm_peak_fraction"],
+                   "decode_layer_front_hbm_peak_fraction": front["hbm_peak_fraction"]}
         eng.set_fused(True)
-        return {"arm": arm, "round": rnd, "workload": args.workload, "steps": args.steps, "warmup": args.warmup,
+        if eng.weight_format == "fp8":
+            eng.set_fp8_block(False)
+        return {**out, "arm": arm, "round": rnd, "workload": args.workload, "steps": args.steps, "warmup": args.warmup,
                 "tokens": tokens, "seconds": round(dt, 4), "tok_s": round(tokens / dt, 1),
                 "decode_step_us": round(us.value, 1), "weight_format": eng.native_weight_format(),
                 "block_launches": eng.block_launches(), "device": torch.cuda.get_device_name(0)}
@@ -94,8 +127,13 @@ def main() -> None:
             u = [r["decode_step_us"] for r in runs if r["arm"] == arm]
             summary[arm] = {"tok_s": v, "spread_pct": round(100 * (max(v) - min(v)) / min(v), 2),
                             "decode_step_us": u}
+            for key in ("decode_layer_us", "decode_layer_front_us", "decode_layer_hbm_peak_fraction"):
+                w = [r[key] for r in runs if r["arm"] == arm and key in r]
+                if w:
+                    summary[arm][key] = w
         mean = lambda arm: sum(summary[arm]["tok_s"]) / len(summary[arm]["tok_s"])   # noqa: E731
         summary["fp8_vs_bf16"] = round(mean("fp8") / mean("bf16"), 4)
+        summary["fp8_block_vs_bf16"] = round(mean("fp8_block") / mean("bf16"), 4)
         summary["fp8_vs_bf16_per_op"] = round(mean("fp8") / mean("bf16_per_op"), 4)
         f.write(json.dumps(summary) + "\n")
         print(json.dumps(summary), flush=True)
