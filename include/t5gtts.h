@@ -490,7 +490,7 @@ int t5g_engine_set_sampler_path(t5g_engine* e, int32_t single_block);
 /* Decode step layout (fast path; parity mode runs the exact-order kernels): each decoder
  * layer after its self attention -- o-projection, norm, cross-q, PM cross attention,
  * cross-o, norm, gate/up GeGLU, down, norm, the next layer's q|k|v -- as ONE persistent
- * launch with in-launch hand-offs (fused.hip; 1-16 rows with one 16-row MFMA tile per stage;
+ * launch with in-launch hand-offs (fused.hip, fused_kernels.h; 1-16 rows with one 16-row MFMA tile per stage;
  * 17-32 rows with two tiles once t5g_engine_set_block_max_rows(e, 32) allows it, otherwise
  * 17-32 rows fuse the MLP half) or as per-op launches; bitwise equal. Default on. Computes the reference's PMDecoderLayer
  * (hf_export/modeling_t5gemma_voice.py:256-323, [tf] modeling_t5gemma.py:81-97); no

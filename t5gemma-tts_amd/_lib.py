@@ -311,15 +311,20 @@ T5G_EUNSUPPORTED = -3
 # kernel sources each PMC-measured op is built from: a profiles/*_pmc_*.json records their
 # digest when the pass runs, and bench.py quotes that file's traffic only while the sources
 # still hash the same (a kernel change that keeps the kernel's name makes the file stale)
+# (the persistent decode launches: every file fused.hip and fused_p8.hip include from csrc/,
+# tests/test_lib_cpu.py checks the lists against the #include lines)
+_FUSED_MLP = ["fused.hip", "fused_p8.hip", "fused_kernels.h", "fused_sync.h", "fused_norm.h", "fused_gemv.h", "fp8.h",
+              "common.h", "t5g_kernels.h"]
+_FUSED_BLOCK = _FUSED_MLP + ["fused_attn.h", "attn_chunk.h"]
 PMC_SOURCES = {
-    "fused_block": ["fused.hip", "fused_p8.hip", "fp8.h", "attn_chunk.h", "common.h", "t5g_kernels.h"],
-    "fused_block_s": ["fused.hip", "fused_p8.hip", "fp8.h", "attn_chunk.h", "common.h", "t5g_kernels.h"],
-    "fused_mlp": ["fused.hip", "fused_p8.hip", "fp8.h", "common.h", "t5g_kernels.h"],
+    "fused_block": _FUSED_BLOCK,
+    "fused_block_s": _FUSED_BLOCK,
+    "fused_mlp": _FUSED_MLP,
     "xlayer": ["xlayer.hip", "exact_dev.h", "exact_math.h", "common.h", "t5g_kernels.h"],
     "gate_up": ["gemv.hip", "common.h", "t5g_kernels.h"],
     # every source the fast decode step's logits and tokens depend on (fast_token_agreement)
-    "fast_path": ["fused.hip", "fused_p8.hip", "attn.hip", "attn_chunk.h", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
-                  "engine.hip", "engine_state.h", "common.h", "t5g_kernels.h"],
+    "fast_path": _FUSED_BLOCK + ["attn.hip", "gemm.hip", "gemv.hip", "norm.hip", "sampler.hip", "noise.hip",
+                  "engine.hip", "engine_state.h"],
 }
 
 

@@ -17,7 +17,8 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "lib", "libt5gtts.so")
 SOURCES = ["gemm.hip", "gemv.hip", "fp8.hip", "norm.hip", "attn.hip", "sampler.hip", "engine.hip", "engine_hooks.hip", "fused.hip", "fused_rows32.hip", "fused_p8.hip", "exact.hip", "xmm.hip", "xattn.hip", "xlayer.hip", "eager.hip", "noise.hip", "xc2.hip", "xc2enc.hip", "whisper.hip", "host_sampler.cpp"]
-HEADERS = ["common.h", "fp8.h", "attn_chunk.h", "t5g_kernels.h", "engine_state.h", "xc2_common.h", "exact_math.h", "exact_dev.h", "ref_ksplit.h", "sort_emu.h"]
+HEADERS = ["common.h", "fp8.h", "attn_chunk.h", "t5g_kernels.h", "engine_state.h", "xc2_common.h", "exact_math.h", "exact_dev.h", "ref_ksplit.h", "sort_emu.h",
+           "fused_sync.h", "fused_norm.h", "fused_gemv.h", "fused_attn.h", "fused_kernels.h"]
 ARCH = os.environ.get("T5G_ARCH", "gfx950")
 # -ffp-contract=off: HIP's default (fast-honor-pragmas) fuses a*b+c into one fma even
 # through __fmul_rn / __fsub_rn, which changes roundings the reference's CPU kernels keep
@@ -34,13 +35,8 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-# sources that include another source (fused_rows32.hip compiles fused.hip's two-tile kernels,
-# fused_p8.hip its FP8 ones)
-INCLUDED_SOURCES = ["fused.hip"]
-
-
 def _newest_dep() -> float:
-    deps = [os.path.join(CSRC, h) for h in HEADERS + INCLUDED_SOURCES] + \
+    deps = [os.path.join(CSRC, h) for h in HEADERS] + \
         [os.path.join(REPO, "include", h) for h in ("t5gtts.h", "xc2.h", "whisper.h")]
     return max(os.path.getmtime(p) for p in deps if os.path.exists(p))
 

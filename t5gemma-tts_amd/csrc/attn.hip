@@ -654,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(AttnArgs a) {
         const int jl = i * KPB + wave * KPW + kg;
         if constexpr (FLASH && LPK == 32 && G == 2) {
             // the flash launch at the 2b-2b geometry: the key's two heads reduced together
-            // (common.h xsum2_v32, as fused.hip's stage S: the same adds per head), head 0's
+            // (common.h xsum2_v32, as fused_attn.h's stage S: the same adds per head), head 0's
             // score on the even 16-lane rows, head 1's on the odd rows
             const float sr = xsum2_v32(s[0], s[1]);
             if (dl % 16 == 0) sm[dl / 16][jl] = fast_score(sr, a.scale, a.softcap);

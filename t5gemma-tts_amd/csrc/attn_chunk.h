@@ -1,7 +1,7 @@
 // Rounding points of a 64-key decode attention chunk that every placement shares.
 //
 // The per-op launch (attn.hip attn_decode_kernel + attn_flash_finish), stage S of the layer
-// launch (fused.hip fb_self_attn) and the layer launch's cross attention (fused.hip stage A)
+// launch (fused_attn.h fb_self_attn) and the layer launch's cross attention (fused_kernels.h stage A)
 // must return the same bits. These pieces are the register-only expressions where a result is
 // rounded, packed or summed in a fixed order; the sites call them, and each site compiles to
 // the machine code it had with the expression written out. The larger steps of a chunk

@@ -1072,7 +1072,7 @@ static void p8_weight(const bf16_t*& W, const float*& S, const t5g_fp8_linear& x
     S = x.scale;
 }
 
-// the same launch with the cross-attention chain in front (fused.hip fused_block_kernel):
+// the same launch with the cross-attention chain in front (fused_kernels.h fused_block_kernel):
 // o-proj slabs in e->part -> ... -> down slabs in e->part
 FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
@@ -1412,7 +1412,7 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
         }
         const DecodeLaunch launch = decode_layer_launch(e, p, M, l, fa);
         // the rest of the layer (o-projection, cross attention, MLP half, the last norm and the
-        // next layer's q|k|v) as one persistent launch (fused.hip fused_block_kernel), with the
+        // next layer's q|k|v) as one persistent launch (fused_kernels.h fused_block_kernel), with the
         // attention as its stage S in front or as its own launch before it (all three bitwise
         // equal to the per-op launches below)
         if (launch == DL_BLOCK_S || launch == DL_BLOCK) {

@@ -45,7 +45,7 @@ struct DecGemmArgs {
 int gemv_dec(const DecGemmArgs& a, int epi, hipStream_t st);
 size_t gemv_dec_lds_bytes(const DecGemmArgs& a, int rg);
 
-// decode MLP half in one persistent launch (fused.hip): norm of the cross-o slabs ->
+// decode MLP half in one persistent launch (fused.hip; kernels: fused_kernels.h): norm of the cross-o slabs ->
 // gate/up GeGLU -> down slabs, hand-offs in-launch
 struct FusedMlpArgs {
     int M, d, f;              // rows (<= 32), hidden (2304), intermediate (9216)
@@ -68,7 +68,7 @@ struct FusedMlpArgs {
     int grid;                 // 0: one workgroup per CU
     int norm_b0;              // set by fused_mlp: first norm workgroup
     int dbg_seq;              // diagnostic timeline slot (T5G_DBG_TS builds only)
-    // ---- cross-attention chain in front (xattn = 1: fused.hip fused_block_kernel):
+    // ---- cross-attention chain in front (xattn = 1: fused_kernels.h fused_block_kernel):
     //   N1: h1 = h + RMSNorm_post1(o-proj slabs), xn1 = RMSNorm_pre1(h1)
     //   Q:  cross-q fp32 slabs [2][M][q_dim] = xn1 . Wq^T (2 k-slices of 36 k-steps)
     //   A:  att = PMCrossAttention(q slabs, cross K/V) per (row, q head)

@@ -22,14 +22,14 @@
 //
 // What it buys: nine launch boundaries per layer, and every stage's weights requested before
 // the hand-off its activations wait for, so each weight stream is in flight while the previous
-// stage finishes. Hand-offs follow fused.hip / cdna_hip_programming.md Guideline 16 R1: every
+// stage finishes. Hand-offs follow fused_sync.h / cdna_hip_programming.md Guideline 16 R1: every
 // handed-off byte is stored sc1 (write-through) by the wave that computed it, every storing
 // wave drains (vmcnt(0)), the workgroup meets at a barrier, one lane adds to a relaxed
 // agent-scope counter (arrivals spread over up to 8 lines of 128 bytes); the consumer's wave 0
 // polls its lines in one round trip per poll, the workgroup meets it at a barrier, and every
 // load of handed-off bytes is an sc1 load. Each layer has its own counter set; a launch zeroes
 // the NEXT layer's set as it starts (its last user, the previous step's launch of that layer,
-// has completed). Every wait is bounded (fused.hip's sticky timeout word: a wait that gives up
+// has completed). Every wait is bounded (fused_sync.h's sticky timeout word: a wait that gives up
 // makes every later one give up at once; t5g_read_tokens reports T5G_EHANDOFF and engine.py
 // reruns the call on the per-op launches).
 #include "common.h"

@@ -282,14 +282,14 @@ class T5GemmaTTSEngine:
         attention, cross-o, norm, gate/up, down, norm, the next q|k|v) as one persistent
         launch (default; 17-32 rows: the MLP half, or the whole layer with two MFMA tiles per
         stage after set_block_max_rows(32)) or as per-op launches; bitwise equal
-        (csrc/fused.hip). In parity mode the same switch selects the exact-order persistent
+        (csrc/fused.hip, kernels in csrc/fused_kernels.h). In parity mode the same switch selects the exact-order persistent
         layer (csrc/xlayer.hip; 1-8 rows of <= 64 text keys), bitwise equal to the per-op
         exact launches."""
         _lib.check(self.L.t5g_engine_set_fused(self.h, 1 if enable else 0), "set_fused")
 
     def set_block_max_rows(self, n: int) -> None:
         """The largest decode batch the whole-layer launch takes: 16 (default) or 32 (17-32
-        rows then run its two-tile form, csrc/fused_rows32.hip; bitwise equal to the per-op
+        rows then run its two-tile form, csrc/fused_rows32.hip (both: csrc/fused_kernels.h); bitwise equal to the per-op
         launches). Other values raise ValueError."""
         _lib.check(self.L.t5g_engine_set_block_max_rows(self.h, int(n)), "set_block_max_rows")
 
@@ -318,7 +318,7 @@ class T5GemmaTTSEngine:
         return n.value
 
     def set_attn_in_block(self, mode) -> None:
-        """Fast-path decode self attention inside the persistent layer launch (csrc/fused.hip
+        """Fast-path decode self attention inside the persistent layer launch (csrc/fused_attn.h
         stage S): 0 / False its own flash launch, 1 in front of the launch's o-projection,
         2 / True (default) at the end of the previous layer's launch after its q|k|v stage,
         with that layer's o-projection. Bitwise equal in every mode; a call past the tail's

@@ -1,6 +1,6 @@
 """The fast path's chunk scores at the 2b-2b head geometry (8 q / 4 kv heads x 256), where a key's
 two heads are reduced together (csrc/common.h xsum2_v32, in attn.hip's flash launch and in
-fused.hip's stage S: the adds of the lane-split butterfly per head), through
+fused_attn.h's stage S: the adds of the lane-split butterfly per head), through
 t5g_attention_decode_flash against exact fp64 attention and the aten-order form
 (t5g_attention_decode) on the same inputs: at the chunk edges, with chunks that start at an
 arbitrary key (a sliding window), with NaN in the cache slots past each row's length, with a

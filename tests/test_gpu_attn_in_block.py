@@ -1,5 +1,5 @@
 """The fast path's decode self attention as stage S of the persistent layer launch
-(csrc/fused.hip fb_self_attn: the flash launch's arithmetic, one 64-key chunk per 4-wave
+(csrc/fused_attn.h fb_self_attn: the flash launch's arithmetic, one 64-key chunk per 4-wave
 group spread over every workgroup, the holder of a (row, kv head)'s last chunk combining, att_self handed to the o-projection
 in-launch) against the same step with the attention as its own flash launch
 (attn.hip attn_decode_kernel<256, 2, true, true>): tokens and every logit row bitwise equal,

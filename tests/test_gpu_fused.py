@@ -1,4 +1,4 @@
-"""The decode MLP half as one persistent launch (csrc/fused.hip: cross-attention residual
+"""The decode MLP half as one persistent launch (csrc/fused.hip, kernels in csrc/fused_kernels.h: cross-attention residual
 norm -> gate/up GeGLU -> down, with in-launch hand-offs) against the same step as three
 launches (resid_norm + the two register-X GEMVs): tokens and every logit row bitwise equal,
 at the true 2b-2b widths (d 2304, FFN 9216; 2 + 2 layers), for 1, 8, 12 and 16 rows (the

@@ -1,4 +1,4 @@
-"""The whole-layer decode launch with the early weight requests (csrc/fused.hip: a wave that
+"""The whole-layer decode launch with the early weight requests (csrc/fused_kernels.h: a wave that
 stores nothing in cross-o's / gate/up's epilogue requests its gate/up / down weights right
 after the stage's MFMAs, and only the storing waves drain in front of the publish) against the
 per-op launches, at the true 2b-2b widths (2 + 2 layers). Row counts that move the worker maps

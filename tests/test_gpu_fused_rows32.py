@@ -1,4 +1,4 @@
-"""The whole-layer persistent launch at 17-32 rows (csrc/fused.hip fused_block_kernel with two
+"""The whole-layer persistent launch at 17-32 rows (csrc/fused_kernels.h fused_block_kernel with two
 16-row MFMA tiles per GEMV stage, compiled in csrc/fused_rows32.hip; a norm workgroup per two
 rows, a cross-attention workgroup per (row, kv head)), enabled by set_block_max_rows(32),
 against the same step on the per-op launches: tokens and every logit row bitwise equal at the

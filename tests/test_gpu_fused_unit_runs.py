@@ -1,5 +1,5 @@
 """The whole-layer decode launch with waves 8-10 of the workers that run no attention requesting
-their share of the run's gate/up register units in the attention window (csrc/fused.hip: with
+their share of the run's gate/up register units in the attention window (csrc/fused_kernels.h: with
 the LDS copies, crossing cross-o on its barriers alone), against the per-op launches at the true
 2b-2b widths (2 + 2 layers). Row counts: 1 (8 attention workers of 255), 3, 8 (the benchmark's
 map: 64 attention workers, 96 + 88 others with 5 / 4 units), 12 (176 workers with 5 units: 96

@@ -38,6 +38,46 @@ def test_struct_layouts_match_header():
     assert _lib.NormSrcArgs.part.offset == 40 and _lib.NormSrcArgs.resid_out.offset == 88
 
 
+def _csrc_include_closure(src):
+    """`src` and every csrc file its #include "..." lines reach, transitively."""
+    import re
+    from t5gemma_tts_amd import build
+    seen, todo = set(), [src]
+    while todo:
+        name = todo.pop()
+        if name in seen:
+            continue
+        seen.add(name)
+        with open(os.path.join(build.CSRC, name)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                if os.path.exists(os.path.join(build.CSRC, inc)):
+                    todo.append(inc)
+    return seen
+
+
+def test_fused_sources_are_tracked_by_build_and_digest():
+    """The persistent decode launches are built from stage headers: every csrc file the three
+    fused units include must be a rebuild dependency (build.py HEADERS / SOURCES), and every
+    file behind the one-tile kernels must be hashed by the PMC source digests."""
+    from t5gemma_tts_amd import _lib, build
+    units = ["fused.hip", "fused_rows32.hip", "fused_p8.hip"]
+    reach = {u: _csrc_include_closure(u) for u in units}
+    assert all(len(reach[u]) > 5 for u in units), reach   # the closure walk found the headers
+    tracked = set(build.HEADERS) | set(build.SOURCES)
+    for u in units:
+        assert reach[u] <= tracked, (u, sorted(reach[u] - tracked))
+        assert not [f for f in reach[u] - {u} if f.endswith(".hip")], (u, "includes another source")
+    one_tile = reach["fused.hip"] | reach["fused_p8.hip"]
+    for op in ("fused_block", "fused_block_s"):
+        assert one_tile <= set(_lib.PMC_SOURCES[op]), (op, sorted(one_tile - set(_lib.PMC_SOURCES[op])))
+    attention = {"fused_attn.h", "attn_chunk.h"}
+    assert attention <= one_tile
+    assert one_tile - attention <= set(_lib.PMC_SOURCES["fused_mlp"]), \
+        sorted(one_tile - attention - set(_lib.PMC_SOURCES["fused_mlp"]))
+    for op in ("fused_block", "fused_block_s", "fused_mlp", "fast_path"):
+        assert len(_lib.kernel_source_digest(op)) == 16   # every listed file exists
+
+
 def test_packed_bytes():
     from t5gemma_tts_amd import _lib
     L = _lib.lib()

@@ -1,4 +1,4 @@
-"""Block timeline of the fused decode launch (csrc/fused.hip) inside a C3-shaped decode step,
+"""Block timeline of the fused decode launch (csrc/fused.hip, kernels in csrc/fused_kernels.h) inside a C3-shaped decode step,
 on the diagnostic library (T5G_DBG_TS): for the last layer's launch, per numbered point the
 time from the first block start (100 MHz device clock), over all workgroups and over the
 norm workgroups. B <= 16 runs fused_block_kernel (points: 1 Q hand-off seen, 2 O hand-off

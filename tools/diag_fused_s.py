@@ -1,5 +1,5 @@
-"""Timeline of the fast path's persistent layer launch WITH the self attention (csrc/fused.hip
-stage S) inside a C3-shaped decode step at ~527 keys, on the diagnostic library (T5G_DBG_TS):
+"""Timeline of the fast path's persistent layer launch WITH the self attention (csrc/fused_kernels.h,
+csrc/fused_attn.h stage S) inside a C3-shaped decode step at ~527 keys, on the diagnostic library (T5G_DBG_TS):
 for the last launch of the call, per point the time from the first workgroup start (100 MHz
 device clock): 1 row geometry read, 2 q staged, 3 K in + scores, 4 P.V reduced, 5 partials
 drained, 6 ticket seen, 7 att_self published (combiners / one-chunk rows), 8 S left, 9 O1

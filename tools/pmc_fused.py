@@ -1,4 +1,4 @@
-"""Drive the fused decode launch (csrc/fused.hip; at M = 8 the fused_block_kernel) at C3 shape
+"""Drive the fused decode launch (csrc/fused.hip, kernels in csrc/fused_kernels.h; at M = 8 the fused_block_kernel) at C3 shape
 (M = 8, T_x 60, 2b-2b widths) over
 the 26 decoder layers' weights (3.3 GB, beyond the 256 MiB Infinity Cache), as bench.py's
 roofline leg does, so rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE can count its HBM bytes per
