@@ -170,9 +170,11 @@ int64_t t5g_engine_workspace_bytes(const t5g_engine* e);
  * seven weights of a launch are P8), under the switches and stage-S placement rules of the
  * bf16 launch (t5g_engine_set_fused, t5g_engine_set_attn_in_block); layer 0's q|k|v, attention
  * and o-projection and the head stay on the P8 GEMVs, and 17-32 rows stay on the per-op P8
- * launches whatever t5g_engine_set_block_max_rows says (there is no P8 form of the two-tile or
- * the MLP-half launch). t5g_time_decode_layer serves an FP8 engine only with that switch on and
- * <= 16 rows (else T5G_EUNSUPPORTED); t5g_time_decode_mlp is T5G_EUNSUPPORTED in FP8 mode.
+ * launches whatever t5g_engine_set_block_max_rows says (there is no P8 form of the two-tile
+ * whole-layer launch), unless t5g_engine_set_fp8_mlp(e, 1) lets them run the MLP-half launch on
+ * the P8 images (below). t5g_time_decode_layer serves an FP8 engine only with
+ * t5g_engine_set_fp8_block on and <= 16 rows (else T5G_EUNSUPPORTED); t5g_time_decode_mlp serves
+ * one only with t5g_engine_set_fp8_mlp on.
  * More than 32 rows: the bf16 kernels on W_q. No reference-side equivalent. */
 typedef struct {
     const void* p8;        /* P8 codes, t5g_fp8_packed_bytes(N, K) bytes */
@@ -194,6 +196,16 @@ int t5g_engine_weight_format(t5g_engine* e, int32_t* fmt);
  * engine that is not in FP8 mode is T5G_EUNSUPPORTED (t5g_engine_set_fp8_weights(e, NULL)
  * also clears the switch). A change drops the captured graphs. No reference-side equivalent. */
 int t5g_engine_set_fp8_block(t5g_engine* e, int32_t enable);
+/* FP8 mode: let the layers that run per-op launches (1-32 rows) run their MLP half -- the
+ * cross-attention residual norm, gate/up GeGLU and down -- as the persistent MLP-half launch
+ * on the P8 images of gate/up and down (csrc/fused_mlp_p8.hip: fused_mlp_kernel<9> at 1-16
+ * rows, <10> at 17-32), under t5g_engine_set_fused as on a bf16 engine. Default 0. With
+ * t5g_engine_set_fp8_block on as well, 1-16 rows take the whole-layer launch and 17-32 rows
+ * this one. Bitwise equal to the per-op P8 launches and to the bf16 launches on W_q
+ * (tests/test_gpu_fp8_mlp.py). T5G_EINVAL on a NULL engine; enabling on an engine that is not
+ * in FP8 mode is T5G_EUNSUPPORTED (t5g_engine_set_fp8_weights(e, NULL) also clears the switch).
+ * A change drops the captured graphs. No reference-side equivalent. */
+int t5g_engine_set_fp8_mlp(t5g_engine* e, int32_t enable);
 
 /* --- generate() phases --------------------------------------------------------
  * Token batches are PACKED: ntok tokens of B rows, with per-token row index
@@ -508,6 +520,9 @@ int t5g_engine_set_fused(t5g_engine* e, int32_t enable);
  * launch captured into a graph counts once, at capture). */
 int t5g_engine_set_block_max_rows(t5g_engine* e, int32_t n);
 int t5g_engine_block_launches(t5g_engine* e, int64_t* n);
+/* MLP-half launches issued so far, on bf16 or P8 weights (a launch captured into a graph
+ * counts once, at capture). Test / bench hook; no reference-side equivalent. */
+int t5g_engine_mlp_half_launches(t5g_engine* e, int64_t* n);
 /* Test / bench hook: parity-mode persistent layer launches issued so far (a launch captured
  * into a graph counts once, at capture). No reference-side equivalent. */
 int t5g_engine_xlayer_launches(t5g_engine* e, int64_t* n);

@@ -183,7 +183,9 @@ SIGNATURES = {
     "t5g_engine_set_fused": (C.c_int, [_P, _I]),
     "t5g_engine_set_block_max_rows": (C.c_int, [_P, _I]),
     "t5g_engine_set_fp8_block": (C.c_int, [_P, _I]),
+    "t5g_engine_set_fp8_mlp": (C.c_int, [_P, _I]),
     "t5g_engine_block_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "t5g_engine_mlp_half_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_engine_xlayer_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "t5g_time_xlayer": (C.c_int, [_P, _I, _I, _P, C.POINTER(C.c_float)]),
     "t5g_engine_set_attn_in_block": (C.c_int, [_P, _I]),
@@ -311,9 +313,9 @@ T5G_EUNSUPPORTED = -3
 # kernel sources each PMC-measured op is built from: a profiles/*_pmc_*.json records their
 # digest when the pass runs, and bench.py quotes that file's traffic only while the sources
 # still hash the same (a kernel change that keeps the kernel's name makes the file stale)
-# (the persistent decode launches: every file fused.hip and fused_p8.hip include from csrc/,
-# tests/test_lib_cpu.py checks the lists against the #include lines)
-_FUSED_MLP = ["fused.hip", "fused_p8.hip", "fused_kernels.h", "fused_sync.h", "fused_norm.h", "fused_gemv.h", "fp8.h",
+# (the persistent decode launches: every file fused.hip, fused_p8.hip and fused_mlp_p8.hip
+# include from csrc/, tests/test_lib_cpu.py checks the lists against the #include lines)
+_FUSED_MLP = ["fused.hip", "fused_p8.hip", "fused_mlp_p8.hip", "fused_kernels.h", "fused_sync.h", "fused_norm.h", "fused_gemv.h", "fp8.h",
               "common.h", "t5g_kernels.h"]
 _FUSED_BLOCK = _FUSED_MLP + ["fused_attn.h", "attn_chunk.h"]
 PMC_SOURCES = {
@@ -419,11 +421,18 @@ def fused_block_bytes(M: int, T_x: int, d: int = 2304, f: int = 9216, q_dim: int
     return ((n_layers - 1) * mid + last) / n_layers
 
 
-def fused_mlp_bytes(M: int, d: int = 2304, f: int = 9216) -> int:
+def fused_mlp_bytes(M: int, d: int = 2304, f: int = 9216, weight_format: str = "bf16") -> int:
     """Algorithmic HBM bytes of one fused decode-MLP launch (csrc/fused.hip): gate/up and down
     weights, the 4 cross-o slabs, h and the two norm weights in; h and the 8 down slabs out.
-    xn and act are in-launch hand-offs (written and read once each, not counted)."""
-    return 2 * f * d * 2 + d * f * 2 + 4 * M * d * 4 + M * d * 2 + 2 * d * 2 + M * d * 2 + 8 * M * d * 4
+    xn and act are in-launch hand-offs (written and read once each, not counted).
+    weight_format "fp8" (the P8 launch, csrc/fused_mlp_p8.hip): each weight counts 1 byte per
+    element plus its fp32 row scales (4 bytes per output row: 2 f gate/up rows, d down rows)."""
+    if weight_format not in ("bf16", "fp8"):
+        raise ValueError(f"weight_format {weight_format!r}: 'bf16' or 'fp8'")
+    w = 2 * f * d * 2 + d * f * 2
+    if weight_format == "fp8":
+        w = w // 2 + 4 * (2 * f + d)
+    return w + 4 * M * d * 4 + M * d * 2 + 2 * d * 2 + M * d * 2 + 8 * M * d * 4
 
 
 def time_gate_up(X_ptr: int, ldx: int, M: int, W_ptrs, N: int, K: int, Y_ptr: int, iters: int, stream) -> float:

@@ -16,7 +16,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "lib", "libt5gtts.so")
-SOURCES = ["gemm.hip", "gemv.hip", "fp8.hip", "norm.hip", "attn.hip", "sampler.hip", "engine.hip", "engine_hooks.hip", "fused.hip", "fused_rows32.hip", "fused_p8.hip", "exact.hip", "xmm.hip", "xattn.hip", "xlayer.hip", "eager.hip", "noise.hip", "xc2.hip", "xc2enc.hip", "whisper.hip", "host_sampler.cpp"]
+SOURCES = ["gemm.hip", "gemv.hip", "fp8.hip", "norm.hip", "attn.hip", "sampler.hip", "engine.hip", "engine_hooks.hip", "fused.hip", "fused_rows32.hip", "fused_p8.hip", "fused_mlp_p8.hip", "exact.hip", "xmm.hip", "xattn.hip", "xlayer.hip", "eager.hip", "noise.hip", "xc2.hip", "xc2enc.hip", "whisper.hip", "host_sampler.cpp"]
 HEADERS = ["common.h", "fp8.h", "attn_chunk.h", "t5g_kernels.h", "engine_state.h", "xc2_common.h", "exact_math.h", "exact_dev.h", "ref_ksplit.h", "sort_emu.h",
            "fused_sync.h", "fused_norm.h", "fused_gemv.h", "fused_attn.h", "fused_kernels.h"]
 ARCH = os.environ.get("T5G_ARCH", "gfx950")

@@ -91,15 +91,16 @@ def load_codec(codec_dir: Optional[str] = None, codec: str = "44k", device="cuda
 
 def load_model(model_dir: Optional[str] = None, synthetic: Optional[str] = None, device="cuda:0",
                max_text: int = 512, max_audio: Optional[int] = None, seed: int = 7, weight_format: str = "bf16",
-               fp8_block: bool = False):
+               fp8_block: bool = False, fp8_mlp: bool = False):
     """The voice model, sized for the reference CLI's longest request by default (max_audio =
     engine.MAX_AUDIO keys: a 100 s prompt + the 120 s duration cap; 1.3 GB of KV cache at
     batch 1) -- a shorter request runs on its own key bound, not the capacity.
     ``weight_format="fp8"``: the decode step streams FP8 e4m3 weights (fast path only);
-    ``fp8_block=True`` with it: the whole-layer decode launch on those weights (default off)."""
+    ``fp8_block=True`` with it: the whole-layer decode launch on those weights (default off);
+    ``fp8_mlp=True`` with it: the MLP-half decode launch on them (default off)."""
     from .engine import MAX_AUDIO, T5GemmaVoiceForConditionalGeneration
     kw = dict(device=device, max_batch=1, max_text=max_text, max_audio=MAX_AUDIO if max_audio is None else max_audio,
-              weight_format=weight_format, fp8_block=fp8_block)
+              weight_format=weight_format, fp8_block=fp8_block, fp8_mlp=fp8_mlp)
     if synthetic:
         from .config import named_config
         from .weights import synthetic_weights
@@ -116,7 +117,8 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
                   repeat_prompt=0, stop_repetition=3, sample_batch_size=1, seed=1, output_dir="./generated_tts",
                   cut_off_sec=100, dump_tokens=False, lang=None, codec_dir=None, tokenizer_dir=None, synthetic=None,
                   codec="44k", device="cuda:0", whisper_model="large-v3-turbo", model=None, audio_tokenizer=None,
-                  text_tokenizer=None, asr_model=None, parity=True, weight_format="bf16", fp8_block=False):
+                  text_tokenizer=None, asr_model=None, parity=True, weight_format="bf16", fp8_block=False,
+                  fp8_mlp=False):
     """inference_commandline_hf.py:72-242. ``model`` / ``audio_tokenizer`` /
     ``text_tokenizer`` / ``asr_model`` may be passed pre-built (then nothing is loaded).
     ``parity`` (default True, ``--parity False`` on the command line): reproduce the
@@ -129,12 +131,17 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
     ``fp8_block`` (default False, ``--fp8_block True``): with ``weight_format="fp8"``, run the
     whole-layer decode launch on the FP8 weights (engine ``set_fp8_block``); a ValueError with
     any other format.
+    ``fp8_mlp`` (default False, ``--fp8_mlp True``): with ``weight_format="fp8"``, run the MLP
+    half of the per-op decode layers as one launch on the FP8 weights (engine ``set_fp8_mlp``);
+    a ValueError with any other format.
     Returns the path of the written wav."""
     from .weights import WEIGHT_FORMATS
     if weight_format not in WEIGHT_FORMATS:
         raise ValueError(f"weight_format {weight_format!r}: one of {WEIGHT_FORMATS}")
     if fp8_block and weight_format != "fp8":
         raise ValueError("fp8_block needs weight_format 'fp8' (--weight_format fp8)")
+    if fp8_mlp and weight_format != "fp8":
+        raise ValueError("fp8_mlp needs weight_format 'fp8' (--weight_format fp8)")
     if weight_format == "fp8" and parity:
         print("[Info] weight_format fp8 is fast path only: running with parity=False")
         parity = False
@@ -144,7 +151,8 @@ def run_inference(reference_speech=None, target_text="こんにちは、私はAI
 
     seed_everything(seed)
     if model is None:
-        model = load_model(model_dir, synthetic, device, weight_format=weight_format, fp8_block=bool(fp8_block))
+        model = load_model(model_dir, synthetic, device, weight_format=weight_format, fp8_block=bool(fp8_block),
+                           fp8_mlp=bool(fp8_mlp))
     cfg = model.config
     if text_tokenizer is None:
         if synthetic and _none(tokenizer_dir):
@@ -251,6 +259,8 @@ def main(argv=None) -> None:
     args = ap.parse_args(argv)
     if args.fp8_block and args.weight_format != "fp8":
         ap.error("--fp8_block needs --weight_format fp8")
+    if args.fp8_mlp and args.weight_format != "fp8":
+        ap.error("--fp8_mlp needs --weight_format fp8")
     run_inference(**vars(args))
 
 

@@ -826,7 +826,7 @@ extern "C" int t5g_engine_set_fp8_weights(t5g_engine* e, const t5g_fp8_weights* 
     }
     drop_graphs(e);   // captured steps hold the other format's launches
     e->fp8 = w != nullptr;
-    if (!w) e->fp8_block = false;   // the switch belongs to FP8 mode
+    if (!w) e->fp8_block = e->fp8_mlp = false;   // the switches belong to FP8 mode
     e->dec8.clear();
     e->head2_8 = {nullptr, nullptr};
     if (w) {
@@ -847,6 +847,16 @@ extern "C" int t5g_engine_set_fp8_block(t5g_engine* e, int32_t enable) {
     if (enable && !e->fp8) return T5G_EUNSUPPORTED;
     if (e->fp8_block != (enable != 0)) {
         e->fp8_block = enable != 0;
+        drop_graphs(e);   // captured launches follow the flag
+    }
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_set_fp8_mlp(t5g_engine* e, int32_t enable) {
+    if (!e) return T5G_EINVAL;
+    if (enable && !e->fp8) return T5G_EUNSUPPORTED;
+    if (e->fp8_mlp != (enable != 0)) {
+        e->fp8_mlp = enable != 0;
         drop_graphs(e);   // captured launches follow the flag
     }
     return T5G_OK;
@@ -1041,7 +1051,7 @@ static int decode_attention(t5g_engine* e, int M, const bf16_t* K, const bf16_t*
 
 // the decode MLP half of decoder layer l as one persistent launch (fused.hip): cross-o
 // slabs in e->part -> h / xn -> act -> down slabs in e->part; layer l's counter set
-FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
+static FusedMlpArgs fused_mlp_fields(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
     const t5g_layer_weights& L = e->dec[l];
     FusedMlpArgs fa;
@@ -1072,12 +1082,24 @@ static void p8_weight(const bf16_t*& W, const float*& S, const t5g_fp8_linear& x
     S = x.scale;
 }
 
+// FP8 mode with the MLP-half launch on (t5g_engine_set_fp8_mlp): gate/up and down are the
+// Linears' P8 images with their row scales (fused_mlp_p8.hip)
+FusedMlpArgs fused_args(t5g_engine* e, int M, int l) {
+    FusedMlpArgs fa = fused_mlp_fields(e, M, l);
+    if (e->fp8 && e->fp8_mlp) {
+        fa.wfmt = 1;
+        p8_weight(fa.Wgu, fa.sWgu, e->dec8[l].gate_up);
+        p8_weight(fa.Wd, fa.sWd, e->dec8[l].down);
+    }
+    return fa;
+}
+
 // the same launch with the cross-attention chain in front (fused_kernels.h fused_block_kernel):
 // o-proj slabs in e->part -> ... -> down slabs in e->part
 FusedMlpArgs fused_block_args(t5g_engine* e, int M, int l) {
     const t5g_config& c = e->c;
     const t5g_layer_weights& L = e->dec[l];
-    FusedMlpArgs fa = fused_args(e, M, l);
+    FusedMlpArgs fa = fused_mlp_fields(e, M, l);
     fa.xattn = 1;
     fa.o_slabs = e->part;
     fa.post1_w = (const bf16_t*)L.norms[1];
@@ -1198,10 +1220,11 @@ DecodePlan decode_plan(t5g_engine* e, int M, int block_rows, bool switches) {
     p.block = M <= block_rows && (!switches || (p.mlp_half && wq));
     // FP8 mode: the whole-layer launch has a P8 form for one tile only, behind its own switch
     // (t5g_engine_set_fp8_block; block_rows above 16 does not apply); the MLP-half launch has
-    // none. Everything else runs the per-op launches on the P8 GEMVs.
+    // one for both tile counts, behind its own switch too (t5g_engine_set_fp8_mlp). Everything
+    // else runs the per-op launches on the P8 GEMVs.
     if (e->fp8) {
         p.block = p.block && e->fp8_block && M <= 16;
-        p.mlp_half = false;
+        p.mlp_half = p.mlp_half && e->fp8_mlp;
     }
     // stage S at the end of the launches (attn_in_block 2): every layer's launch must take it
     p.tail = p.block && e->attn_in_block == 2 && (!switches || e->attn_flash);
@@ -1440,6 +1463,7 @@ static int decode_pass(t5g_engine* e, int M, hipStream_t st) {
         // --- norm + GeGLU MLP as one persistent launch (fused.hip; bitwise equal to the three
         // launches below); -1: a shape / device the launch is not built for
         const int rc = launch == DL_MLP_HALF ? fused_mlp(fa, st) : -1;
+        if (rc == 0) ++e->mlp_launches;
         if (rc != 0) {
             if (rc != -1) RC(rc);
             RC(resid(s_o, L.norms[3], L.norms[4]));
@@ -1751,6 +1775,12 @@ extern "C" int t5g_engine_attn_in_block_launches(t5g_engine* e, int64_t* n) {
 extern "C" int t5g_engine_block_launches(t5g_engine* e, int64_t* n) {
     if (!e || !n) return T5G_EINVAL;
     *n = e->blk_launches;
+    return T5G_OK;
+}
+
+extern "C" int t5g_engine_mlp_half_launches(t5g_engine* e, int64_t* n) {
+    if (!e || !n) return T5G_EINVAL;
+    *n = e->mlp_launches;
     return T5G_OK;
 }
 

@@ -169,7 +169,8 @@ extern "C" int t5g_time_xlayer(t5g_engine* e, int32_t B, int32_t iters, void* st
 // launch streams its weights from HBM (2.2 GB of gate/up + down > the 256 MiB Infinity Cache)
 extern "C" int t5g_time_decode_mlp(t5g_engine* e, int32_t B, int32_t iters, void* stream, float* avg_us) {
     if (!e || iters <= 0 || !avg_us || B <= 0 || B > e->c.max_batch || e->c.n_dec_layers < 2) return T5G_EINVAL;
-    if (e->fp8) return T5G_EUNSUPPORTED;   // the MLP-half launch streams bf16 weights only
+    // FP8 mode: only with t5g_engine_set_fp8_mlp on (fused_args then carries the P8 images)
+    if (e->fp8 && !e->fp8_mlp) return T5G_EUNSUPPORTED;
     e->decode_state_invalid = true;
     hipStream_t st = (hipStream_t)stream;
     const int L = e->c.n_dec_layers;

@@ -92,6 +92,7 @@ struct t5g_engine {
     // with the MLP-half launch
     int block_max_rows = 16;
     int64_t blk_launches = 0;   // whole-layer launches issued (t5g_engine_block_launches)
+    int64_t mlp_launches = 0;   // MLP-half launches issued, either format (t5g_engine_mlp_half_launches)
     int64_t s_launches = 0;   // persistent layer launches run with stage S (tests)
     int s_mode_used = 0;      // the last decode pass's stage-S placement: 2 tail, 1 front, 0 none
     float* afpart = nullptr;    // [B][Hkv][nsplit][G][D]
@@ -143,9 +144,11 @@ struct t5g_engine {
     // Linears; the P16 pointers above are then the images of the same W_q. The fast decode
     // step runs its register-X GEMV sites and the head on them: per-op launches at every
     // batch size, unless fp8_block (t5g_engine_set_fp8_block) lets 1-16 rows take the
-    // whole-layer launch on the P8 images (fused_p8.hip)
+    // whole-layer launch on the P8 images (fused_p8.hip) and fp8_mlp (t5g_engine_set_fp8_mlp)
+    // lets the per-op layers of 1-32 rows run the MLP-half launch on them (fused_mlp_p8.hip)
     bool fp8 = false;
     bool fp8_block = false;
+    bool fp8_mlp = false;
     std::vector<t5g_fp8_layer> dec8;
     t5g_fp8_linear head2_8 = {nullptr, nullptr};
 };

@@ -7,8 +7,9 @@
 // unit of their own (fused_rows32.hip): instantiated beside the one-tile kernels they change the
 // compiler's inlining decisions for those, and the one-tile kernels stay the code they were.
 // The FP8 (P8, fp8.h) instantiations of the one-tile kernels are a third translation unit for
-// the same reason (fused_p8.hip). Both carry kernels only, so the three units must stay
-// separately compiled; the launcher and the diagnostic symbols stay here.
+// the same reason (fused_p8.hip), and the P8 instantiations of fused_mlp_kernel a fourth
+// (fused_mlp_p8.hip). They carry kernels only, so the four units must stay separately compiled;
+// the launcher and the diagnostic symbols stay here.
 #include "common.h"
 
 namespace t5g {
@@ -38,6 +39,8 @@ namespace t5g {
 
 fused_block_fn fused_block_rows32_kernel(int sv);   // fused_rows32.hip
 fused_block_fn fused_block_p8_kernel(int sv);       // fused_p8.hip
+typedef void (*fused_mlp_fn)(FusedMlpArgs);
+fused_mlp_fn fused_mlp_p8_kernel(int MT);           // fused_mlp_p8.hip
 
 constexpr size_t FM_LDS_MAX = 160 * 1024;
 
@@ -76,11 +79,12 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
         !a.sync_next || !a.timeout || a.sync_next == a.sync)
         return -1;
     if (a.NGgu * 8 != a.f || a.NGd * 16 != a.d) return -1;
-    // P8 weights: the one-tile whole-layer kernels only (no MLP-half or two-tile form), every
-    // weight of the launch with its row scales
-    if (a.wfmt != 0 &&
-        (a.wfmt != 1 || a.M > 16 || !a.xattn || !a.sWgu || !a.sWd || !a.sWq || !a.sWo || (a.Wo1 && !a.sWo1) ||
-         (a.Wqkv && !a.sWqkv) || (a.self_tail && !a.sWo1n)))
+    // P8 weights, every weight of the launch with its row scales: the MLP-half kernels at one
+    // or two tiles (gate/up and down), the whole-layer kernels at one tile only (there is no
+    // two-tile P8 block)
+    if (a.wfmt != 0 && (a.wfmt != 1 || !a.sWgu || !a.sWd)) return -1;
+    if (a.wfmt != 0 && a.xattn &&
+        (a.M > 16 || !a.sWq || !a.sWo || (a.Wo1 && !a.sWo1) || (a.Wqkv && !a.sWqkv) || (a.self_tail && !a.sWo1n)))
         return -1;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev))
@@ -147,10 +151,10 @@ static int fused_mlp_launch(const FusedMlpArgs& a_in, hipStream_t st, bool launc
     // norm rows on workgroups with one gate/up unit fewer (their weight stream starts after
     // the norm): the last ones
     a.norm_b0 = nb - a.M;
-    auto* fn = MT == 1 ? fused_mlp_kernel<1> : fused_mlp_kernel<2>;
+    fused_mlp_fn fn = a.wfmt ? fused_mlp_p8_kernel(MT) : MT == 1 ? fused_mlp_kernel<1> : fused_mlp_kernel<2>;
     if (dev < 0 || dev >= 64) return -1;
-    static bool attr[64][2] = {};
-    if (!kernel_ready((const void*)fn, shm, attr[dev][MT - 1])) return -1;
+    static bool attr[64][2][2] = {};   // (device, format, tiles)
+    if (!kernel_ready((const void*)fn, shm, attr[dev][a.wfmt ? 1 : 0][MT - 1])) return -1;
     if (!launch) return 0;
     hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(FM_NW * 64), shm, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -60,37 +60,73 @@ __device__ __forceinline__ void fb_epilogue(int g0, int gs, int nu, int M, void*
     }
 }
 
+// Weight format of a GEMV stage (WF): P16 bf16 fragments, or P8 (fp8.h) --
+// e4m3 codes in the same lane order, 8 bytes per lane and k-step, plus the lane's fp32 row
+// scale per unit; p8_to_bf16 in front of each MFMA gives exactly the P16 fragment of the
+// dequantised weights W_q, so a P8 stage is bitwise the P16 stage on W_q. A stage's weight
+// registers FbW<WF, UMAX, SPU>: P16 the fragments, P8 half as many registers for the codes plus
+// one scale per unit.
+constexpr int WF_P16 = 0, WF_P8 = 1;
+template <int WF, int UMAX, int SPU>
+struct FbW {
+    typedef bf16x8_s frag;   // one lane's registers of a (unit, k-step) fragment
+    frag w[UMAX][SPU];
+};
+template <int UMAX, int SPU>
+struct FbW<WF_P8, UMAX, SPU> {
+    typedef u32x2 frag;
+    frag w[UMAX][SPU];
+    float s[UMAX];
+};
+__device__ __forceinline__ void fb_wload(bf16x8_s& w, __amdgpu_buffer_rsrc_t wr, int off) {
+    w = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, AUX_NT));
+}
+__device__ __forceinline__ void fb_wload(u32x2& w, __amdgpu_buffer_rsrc_t wr, int off) {
+    w = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(wr, off, 0, AUX_NT));
+}
+
 // One register-resident-X GEMV stage (gemv_rx_kernel's arithmetic): the workgroup's nu
 // units g = g0 + i * gs of W (KB k-steps of which [kb_lo, kb_lo + KBs) are summed), X rows from
 // `X` (handed off in this launch: sc1 loads), partial sums to LDS `red`, then the
 // epilogue. `wait` runs in wave 0 BEFORE its weight requests (the poll must not queue
 // behind them); the other waves request their weights first.
-template <int MT, int EPI, int SPU, int UMAX, typename Wait, typename Ts>
-__device__ __forceinline__ bool fm_gemv(const bf16_t* W, int NG, int KB, int kb_lo, int KBs, int g0, int gs, int nu,
-                                        const bf16_t* X, int ldx, int xbytes, int M, void* Y, int ldy, int ybytes,
+// WF = P8 (S: the row scales, null for P16): fb_issue<.., WF_P8>'s requests -- the same (wave,
+// unit, k-step) fragments as 8-byte loads from the code image, the lane's row scale once per
+// unit -- and each fragment converted in front of the MFMA that takes it, for every tile;
+// nothing else differs from the P16 stage.
+template <int MT, int EPI, int SPU, int UMAX, int WF = WF_P16, typename Wait, typename Ts>
+__device__ __forceinline__ bool fm_gemv(const bf16_t* W, const float* S, int NG, int KB, int kb_lo, int KBs, int g0, int gs,
+                                        int nu, const bf16_t* X, int ldx, int xbytes, int M, void* Y, int ldy, int ybytes,
                                         int N, f32x4* red, Wait wait, Ts ts, int ts0) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int xr = lane & 15;
-    const __amdgpu_buffer_rsrc_t wr = frag_rsrc(W, (uint32_t)NG * (uint32_t)KB * 1024u);
-    auto wbatch = [&](int i, bf16x8_s(&w)[SPU]) __attribute__((always_inline)) {
+    typedef typename FbW<WF, 1, 1>::frag WT;
+    constexpr int FB = sizeof(WT);
+    const __amdgpu_buffer_rsrc_t wr = frag_rsrc(W, (uint32_t)NG * (uint32_t)KB * (64u * FB));
+    auto wbatch = [&](int i, WT(&w)[SPU], float& sc) __attribute__((always_inline)) {
         const int g = g0 + i * gs;
 #pragma unroll
         for (int j = 0; j < SPU; ++j) {
             const int kb = wave + j * FM_NW;
-            const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * 16 : (int)0xfffffff0u;
-            w[j] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, AUX_NT));
+            const int off = (i < nu && kb < KBs) ? ((g * KB + kb_lo + kb) * 64 + lane) * FB : (int)0xfffffff0u;
+            fb_wload(w[j], wr, off);
+        }
+        if constexpr (WF == WF_P8) {
+            const __amdgpu_buffer_rsrc_t sr = frag_rsrc(S, (uint32_t)NG * 64u);
+            sc = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(sr, (g * 16 + (lane & 15)) * 4, 0, 0));
         }
     };
     bool ok = true;
     if (wave == 0) ok = wait();
     ts(ts0);
-    bf16x8_s wa[SPU], wb[SPU];
-    bf16x8_s wall[UMAX > 0 ? UMAX : 1][SPU];
+    WT wa[SPU], wb[SPU];
+    WT wall[UMAX > 0 ? UMAX : 1][SPU];
+    float sa, sb, sall[UMAX > 0 ? UMAX : 1];   // (P8: the lane's row scale of each unit in flight)
     if constexpr (UMAX > 0) {
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i) wbatch(i, wall[i]);
+        for (int i = 0; i < UMAX; ++i) wbatch(i, wall[i], sall[i]);
     } else {
-        wbatch(0, wa);
+        wbatch(0, wa, sa);
     }
     wg_barrier();   // the hand-off is complete (or abandoned) for every wave past here
     // this wave's X fragments: sc1 loads of bytes other workgroups stored sc1
@@ -109,24 +145,27 @@ __device__ __forceinline__ bool fm_gemv(const bf16_t* W, int NG, int KB, int kb_
             xf[t][j] = (row < M && wave + j * FM_NW < KBs) ? v : z8;
         }
     }
-    auto mul = [&](int i, bf16x8_s(&w)[SPU]) __attribute__((always_inline)) {
+    auto mul = [&](int i, WT(&w)[SPU], float sc) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < SPU; ++j) acc = mfma16(w[j], xf[t][j], acc);
+            for (int j = 0; j < SPU; ++j) {
+                if constexpr (WF == WF_P8) acc = mfma16(p8_to_bf16(w[j], sc), xf[t][j], acc);
+                else acc = mfma16(w[j], xf[t][j], acc);
+            }
             if (i < nu) red[((i * MT + t) * FM_NW + wave) * 64 + lane] = acc;
         }
     };
     if constexpr (UMAX > 0) {
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i) mul(i, wall[i]);
+        for (int i = 0; i < UMAX; ++i) mul(i, wall[i], sall[i]);
     } else {
         for (int i = 0; i < nu; i += 2) {
-            wbatch(i + 1, wb);
-            mul(i, wa);
-            wbatch(i + 2, wa);
-            mul(i + 1, wb);
+            wbatch(i + 1, wb, sb);
+            mul(i, wa, sa);
+            wbatch(i + 2, wa, sa);
+            mul(i + 1, wb, sb);
         }
     }
     __syncthreads();
@@ -172,29 +211,6 @@ __device__ __forceinline__ bool fm_gemv(const bf16_t* W, int NG, int KB, int kb_
         }
     }
     return ok;
-}
-
-// Weight format of the block kernel's GEMV stages (WF): P16 bf16 fragments, or P8 (fp8.h) --
-// e4m3 codes in the same lane order, 8 bytes per lane and k-step, plus the lane's fp32 row
-// scale per unit; p8_to_bf16 in front of each MFMA gives exactly the P16 fragment of the
-// dequantised weights W_q, so a P8 stage is bitwise the P16 stage on W_q. A stage's weight
-// registers FbW<WF, UMAX, SPU>: P16 the fragments, P8 half as many registers for the codes plus
-// one scale per unit.
-constexpr int WF_P16 = 0, WF_P8 = 1;
-template <int WF, int UMAX, int SPU>
-struct FbW {
-    bf16x8_s w[UMAX][SPU];
-};
-template <int UMAX, int SPU>
-struct FbW<WF_P8, UMAX, SPU> {
-    u32x2 w[UMAX][SPU];
-    float s[UMAX];
-};
-__device__ __forceinline__ void fb_wload(bf16x8_s& w, __amdgpu_buffer_rsrc_t wr, int off) {
-    w = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, AUX_NT));
-}
-__device__ __forceinline__ void fb_wload(u32x2& w, __amdgpu_buffer_rsrc_t wr, int off) {
-    w = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(wr, off, 0, AUX_NT));
 }
 
 // Split form of fm_gemv: the weight requests (waves < NWG) ...

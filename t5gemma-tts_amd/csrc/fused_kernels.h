@@ -18,12 +18,16 @@
 // per-wave k-step chains, the same fixed-order wave reductions, the same norm reductions),
 // so the fused launch is bitwise equal to the three launches (tests/test_gpu_fused.py).
 //
-// Weight formats: fused_mlp_kernel and the two-tile fused_block_kernel stream bf16 (P16)
-// weights only. The one-tile fused_block_kernel also has a P8 form (FP8 e4m3 codes + row
-// scales, fp8.h; fused_p8.hip, FusedMlpArgs::wfmt = 1, opt-in through
-// t5g_engine_set_fp8_block): all seven weights of a launch as P8 images, 8-byte requests in
-// the places of the 16-byte ones, each fragment converted in front of its MFMA -- bitwise
-// the bf16 kernel on the dequantised weights (tests/test_gpu_fp8_block.py).
+// Weight formats: the two-tile fused_block_kernel streams bf16 (P16) weights only. The
+// one-tile fused_block_kernel also has a P8 form (FP8 e4m3 codes + row scales, fp8.h;
+// fused_p8.hip, FusedMlpArgs::wfmt = 1, opt-in through t5g_engine_set_fp8_block): all seven
+// weights of a launch as P8 images, 8-byte requests in the places of the 16-byte ones, each
+// fragment converted in front of its MFMA -- bitwise the bf16 kernel on the dequantised weights
+// (tests/test_gpu_fp8_block.py). fused_mlp_kernel has a P8 form for both tile counts
+// (fused_mlp_p8.hip, wfmt = 1 without xattn, opt-in through t5g_engine_set_fp8_mlp): gate/up
+// and down as P8 images through fm_gemv<.., WF_P8>, the same requests, hand-offs and sums
+// (tests/test_gpu_fp8_mlp.py); the two-tile P8 kernel holds its gate/up units resident, which
+// the two-tile bf16 kernel has no registers for.
 #pragma once
 #include "fused_sync.h"
 #include "fused_norm.h"
@@ -32,8 +36,18 @@
 
 namespace t5g {
 
-template <int MT>
+//
+// One template parameter V = MT + 8 WF (MT: 16-row tiles, 1 or 2), so the bf16 kernels keep
+// their names fused_mlp_kernel<1> and <2> (bench.py, the profiles and tools/ name them) and their
+// code; the P8 kernels are fused_mlp_kernel<9> and <10>.
+template <int V>
 __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
+    constexpr int MT = V & 7, WF = V >> 3;
+    // gate/up units resident in registers (0: streamed two batches deep). Two tiles of X beside
+    // five P16 units do not fit 168 registers; five P8 units (60 codes + 5 scales) do, and are
+    // all requested before the N2 wait, as at one tile
+    constexpr int UG = (MT == 1 || WF == WF_P8) ? 5 : 0;
+    static_assert((MT == 1 || MT == 2) && (WF == WF_P16 || WF == WF_P8), "one or two 16-row tiles, P16 or P8");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;                             // GEMV partial sums
     float* nred = (float*)smem;                            // norm stage: 2 x 32 floats (before the GEMVs)
@@ -69,8 +83,8 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
     const int ubase = rest / nr, uextra = rest - ubase * nr;
     const int nu_g = bu < nr ? ubase + (bu < uextra ? 1 : 0) : FM_NORM_UNITS;
     const int g_lo = bu < nr ? bu * ubase + min(bu, uextra) : rest + (bu - nr) * FM_NORM_UNITS;
-    bool ok = fm_gemv<MT, EPI_GEGLU, SPUg, MT == 1 ? 5 : 0>(
-        a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, a.M * d * 2, a.M, a.act, f, a.M * f * 2, 2 * f, red,
+    bool ok = fm_gemv<MT, EPI_GEGLU, SPUg, UG, WF>(
+        a.Wgu, a.sWgu, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, a.M * d * 2, a.M, a.act, f, a.M * f * 2, 2 * f, red,
         [&]() { return fm_wait_n<1>(a.sync, L_N2, Mu, tmo, 1u); }, ts, 2);
     drain_vm();                // act stores of every wave (R1)
     __syncthreads();
@@ -89,8 +103,8 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_mlp_kernel(FusedMlpArgs a) {
     if (s < FM_DS) {
         const int KBd = f / 32, per = KBd / FM_DS;
         constexpr int SPUd = 36 / FM_NW;
-        ok &= fm_gemv<MT, EPI_F32, SPUd, 5>(
-            a.Wd, a.NGd, KBd, s * per, per, j, dg, (a.NGd - j + dg - 1) / dg, a.act, f, a.M * f * 2, a.M, a.part_out + (long)s * a.M * d, d,
+        ok &= fm_gemv<MT, EPI_F32, SPUd, 5, WF>(
+            a.Wd, a.sWd, a.NGd, KBd, s * per, per, j, dg, (a.NGd - j + dg - 1) / dg, a.act, f, a.M * f * 2, a.M, a.part_out + (long)s * a.M * d, d,
             0, d, red, [&]() { return fm_wait_n<1>(a.sync, L_SL0 + s, (unsigned)units_per_slice, tmo, 2u + s); }, ts,
             4);
     }
@@ -615,7 +629,7 @@ __global__ __launch_bounds__(FM_NW * 64) void fused_block_kernel(FusedMlpArgs a)
         // two tiles: fused_mlp_kernel<2>'s stage (units streamed two batches deep, both tiles'
         // partial sums in `red`), the first unit requested before the N2 wait
         ok &= fm_gemv<MT, EPI_GEGLU, 6, 0>(
-            a.Wgu, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, M * d * 2, M, a.act, f, M * f * 2, 2 * f, red,
+            a.Wgu, nullptr, NGg, KBg, 0, KBg, g_lo, 1, nu_g, a.xn, d, M * d * 2, M, a.act, f, M * f * 2, 2 * f, red,
             [&]() { return fm_wait_n<1>(a.sync, L_N2, (unsigned)M, tmo, 5u); }, [](int) {}, 3);
         T5G_TS(4);
     }

@@ -130,8 +130,9 @@ struct FusedMlpArgs {
     int self_tail;
     const bf16_t* Wo1n;       // the next layer's packed self o_proj
     float* o1n;
-    // ---- FP8 weights (wfmt = 1: fused_p8.hip; xattn only, <= 16 rows): ALL seven weight
-    //   pointers above (Wo1, Wq, Wo, Wgu, Wd, Wqkv, Wo1n) are then P8 code images (fp8.h) and
+    // ---- FP8 weights (wfmt = 1: fused_p8.hip with xattn, <= 16 rows; fused_mlp_p8.hip without,
+    //   <= 32 rows, Wgu and Wd alone): ALL weight pointers of the launch (Wo1, Wq, Wo, Wgu, Wd,
+    //   Wqkv, Wo1n) are then P8 code images (fp8.h) and
     //   each non-null one has its fp32 row scales here; no mixed launch. At the end of the
     //   block, so the bf16 kernels' argument offsets are the ones they had without it.
     int wfmt;                 // 0: P16 bf16 images, 1: P8

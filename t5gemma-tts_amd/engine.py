@@ -90,11 +90,11 @@ class T5GemmaTTSEngine:
     def __init__(self, cfg: VoiceConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0",
                  max_batch: int = 8, max_text: int = 128, max_audio: int = 1024, max_gen: Optional[int] = None,
                  free_source: bool = False, shared_from: Optional["T5GemmaTTSEngine"] = None,
-                 weight_format: str = "bf16", fp8_block: bool = False):
+                 weight_format: str = "bf16", fp8_block: bool = False, fp8_mlp: bool = False):
         """``shared_from``: reuse another engine's packed weights on the same device (e.g. a
         second KV arena / batch slot set without a second 10.6 GB weight copy); it must have
-        the same ``weight_format``. ``fp8_block`` is launch state, not weights: a twin takes
-        its own.
+        the same ``weight_format``. ``fp8_block`` and ``fp8_mlp`` are launch state, not weights:
+        a twin takes its own.
         ``weight_format="fp8"`` (opt-in, fast path only): the weights a decode step streams --
         ``weights.fp8_quantized_names`` -- are quantised at load to FP8 e4m3 with power-of-two
         row scales (csrc/fp8.hip) and the decode step's GEMVs and head stream those; every
@@ -102,12 +102,17 @@ class T5GemmaTTSEngine:
         those of a bf16 engine built from ``weights.fp8_rounded_state_dict(cfg, sd)``; parity
         mode is refused. Needs the 2b-2b widths (``weights.fp8_supported``).
         ``fp8_block=True`` (``weight_format="fp8"`` only, default off): ``set_fp8_block(True)``
-        at creation -- decode batches of 1-16 rows run the whole-layer launch on the FP8 images."""
+        at creation -- decode batches of 1-16 rows run the whole-layer launch on the FP8 images.
+        ``fp8_mlp=True`` (``weight_format="fp8"`` only, default off): ``set_fp8_mlp(True)`` at
+        creation -- the layers on per-op launches (1-32 rows) run the MLP-half launch on them."""
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format {weight_format!r}: one of {WEIGHT_FORMATS}")
         if fp8_block and weight_format != "fp8":
             raise ValueError("fp8_block=True needs weight_format='fp8'")
+        if fp8_mlp and weight_format != "fp8":
+            raise ValueError("fp8_mlp=True needs weight_format='fp8'")
         self._fp8_block_init = bool(fp8_block)
+        self._fp8_mlp_init = bool(fp8_mlp)
         if weight_format == "fp8" and not fp8_supported(cfg):
             raise ValueError("weight_format='fp8' needs hidden 2304, intermediate 9216, q_dim 2048 (the widths the "
                              "decode step's register-X GEMVs are built for)")
@@ -272,6 +277,8 @@ class T5GemmaTTSEngine:
             _lib.check(rc, "set_fp8_weights")
         if self._fp8_block_init:
             self.set_fp8_block(True)
+        if self._fp8_mlp_init:
+            self.set_fp8_mlp(True)
         ld = C.c_int32()
         self._logits_ptr = self.L.t5g_logits_ptr(h, C.byref(ld))
         self.logits_ld = ld.value
@@ -296,12 +303,30 @@ class T5GemmaTTSEngine:
     def set_fp8_block(self, enable: bool) -> None:
         """``weight_format="fp8"`` engines: let decode batches of 1-16 rows run the whole-layer
         persistent launch on the FP8 images (csrc/fused_p8.hip) instead of the per-op FP8
-        launches (default off; 17-32 rows stay per-op). Bitwise equal to both the per-op FP8
+        launches (default off; 17-32 rows stay per-op unless ``set_fp8_mlp``). Bitwise equal to both the per-op FP8
         launches and a bf16 engine on the rounded weights. Raises ValueError on a bf16 engine."""
         rc = self.L.t5g_engine_set_fp8_block(self.h, 1 if enable else 0)
         if rc == _lib.T5G_EUNSUPPORTED:
             raise ValueError("set_fp8_block: the engine does not hold FP8 weights (weight_format='fp8')")
         _lib.check(rc, "set_fp8_block")
+
+    def set_fp8_mlp(self, enable: bool) -> None:
+        """``weight_format="fp8"`` engines: let the layers that run per-op launches (1-32 rows;
+        with ``set_fp8_block`` on, 17-32) run their MLP half -- norm, gate/up GeGLU, down -- as
+        the persistent MLP-half launch on the FP8 images (csrc/fused_mlp_p8.hip) instead of three
+        per-op launches (default off). Bitwise equal to both the per-op FP8 launches and a bf16
+        engine on the rounded weights. Raises ValueError on a bf16 engine."""
+        rc = self.L.t5g_engine_set_fp8_mlp(self.h, 1 if enable else 0)
+        if rc == _lib.T5G_EUNSUPPORTED:
+            raise ValueError("set_fp8_mlp: the engine does not hold FP8 weights (weight_format='fp8')")
+        _lib.check(rc, "set_fp8_mlp")
+
+    def mlp_half_launches(self) -> int:
+        """Fast-path MLP-half launches issued so far, on bf16 or FP8 weights (test / bench hook;
+        a launch captured into a graph counts once)."""
+        n = C.c_int64()
+        _lib.check(self.L.t5g_engine_mlp_half_launches(self.h, C.byref(n)), "mlp_half_launches")
+        return n.value
 
     def block_launches(self) -> int:
         """Fast-path whole-layer launches issued so far, with or without the self attention
@@ -712,7 +737,8 @@ class T5GemmaVoiceForConditionalGeneration:
     safetensors, no pickle); ``inference_tts`` keeps the reference signature
     and return shapes (:565-862). ``weight_format="fp8"`` (also through ``from_pretrained``)
     is passed to the engine: FP8 e4m3 decode weights, fast path only; ``fp8_block=True`` goes
-    with it the same way (the whole-layer launch on the FP8 images, off by default)."""
+    with it the same way (the whole-layer launch on the FP8 images, off by default), and so
+    does ``fp8_mlp=True`` (the MLP-half launch on them, off by default)."""
 
     def __init__(self, cfg: VoiceConfig, state_dict, device="cuda:0", **engine_kw):
         self.config = cfg
