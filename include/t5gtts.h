@@ -458,6 +458,9 @@ typedef struct {
     float scale;
     void* out;                /* bf16 [B][n_heads * head_dim] */
     void* work;               /* fp32 scores + chunk maxima, t5g_attention_decode_work_bytes() */
+    float softcap;            /* 0: none (sdpa numerics); >0: the eager score of the fast path (csrc/common.h
+                                 fast_score: bf16 q.k, x scale, / softcap, tanh, x softcap, each rounded to
+                                 bf16); negative or not finite: T5G_EINVAL */
 } t5g_attn_decode_args;
 int64_t t5g_attention_decode_work_bytes(int32_t B, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
                                         int32_t cap);

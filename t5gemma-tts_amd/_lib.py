@@ -104,7 +104,7 @@ class AttnDecodeArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("n_heads", C.c_int32), ("n_kv_heads", C.c_int32), ("head_dim", C.c_int32),
                 ("q", C.c_void_p), ("k_cache", C.c_void_p), ("v_cache", C.c_void_p), ("cap", C.c_int32),
                 ("kv_len", C.c_void_p), ("causal", C.c_int32), ("window", C.c_int32), ("scale", C.c_float),
-                ("out", C.c_void_p), ("work", C.c_void_p)]
+                ("out", C.c_void_p), ("work", C.c_void_p), ("softcap", C.c_float)]
 
 
 class AttnPackedArgs(C.Structure):

@@ -293,7 +293,7 @@ extern "C" int t5g_attention_decode_flash(const t5g_attn_decode_args* g, void* s
 static int attention_decode_abi(const t5g_attn_decode_args* g, bool flash, void* stream) {
     if (!g || !g->q || !g->k_cache || !g->v_cache || !g->kv_len || !g->out || !g->work) return T5G_EINVAL;
     if (g->B <= 0 || g->n_kv_heads <= 0 || g->n_heads % g->n_kv_heads || g->cap <= 0 ||
-        g->cap > SDPA_KV_BLOCK * SDPA_MAX_BLOCKS)
+        g->cap > SDPA_KV_BLOCK * SDPA_MAX_BLOCKS || !(g->softcap >= 0.f && g->softcap < INFINITY))   // negative, NaN or infinite
         return T5G_EINVAL;
     AttnArgs a;
     memset(&a, 0, sizeof(a));
@@ -311,6 +311,7 @@ static int attention_decode_abi(const t5g_attn_decode_args* g, bool flash, void*
     a.causal = g->causal;
     a.window = g->window;
     a.scale = g->scale;
+    a.softcap = g->softcap;   // the score of common.h fast_score; a.eager stays 0 (that is attn_kernel's variant)
     a.O = (bf16_t*)g->out;
     a.ldo = a.ldq;
     a.chunk = 64;

@@ -124,20 +124,26 @@ def _mid_config():
     return cfg, synthetic_weights(cfg, meta["weight_seed"])
 
 
-def mid_config(window=None):
+def mid_config(window=None, attn_implementation=None):
     """(cfg, sd) of golden_mid, made once per process (sd is 657 M synthetic parameters that the
-    engine only reads); window: the sliding layers' window instead of the config's (the weights
-    do not depend on it)."""
+    engine only reads); window: the sliding layers' window instead of the config's;
+    attn_implementation: "eager" (the 50.0 tanh logit softcap on) or "sdpa" instead of the
+    config's (the weights depend on neither)."""
     cfg, sd = _mid_config()
+    kw = {}
     if window is not None:
-        cfg = dataclasses.replace(cfg, backbone=dataclasses.replace(cfg.backbone, sliding_window=window))
+        kw["sliding_window"] = window
+    if attn_implementation is not None:
+        kw["attn_implementation"] = attn_implementation
+    if kw:
+        cfg = dataclasses.replace(cfg, backbone=dataclasses.replace(cfg.backbone, **kw))
     return cfg, sd
 
 
-def mid_engine(max_batch, max_audio=128, window=None, **engine_kw):
+def mid_engine(max_batch, max_audio=128, window=None, attn_implementation=None, **engine_kw):
     """(cfg, a fresh engine) on golden_mid with max_text 64 and max_gen 40."""
     from t5gemma_tts_amd.engine import T5GemmaTTSEngine
-    cfg, sd = mid_config(window)
+    cfg, sd = mid_config(window, attn_implementation)
     return cfg, T5GemmaTTSEngine(cfg, sd, device="cuda:0", max_batch=max_batch, max_text=64, max_audio=max_audio,
                                  max_gen=40, **engine_kw)
 

@@ -5,7 +5,9 @@ no GPU, what those tests rely on before they launch anything -- that a window on
 shorter moves every marked query of the chosen seeds by ten times the bound, that a lost block
 rescale moves the windowed block cases as far, that the slab values tell a slab order, and that
 the share of RoPE pairs next to a bf16 tie is what the safe-set rule expects. Also the decode
-attention call and its fp64 reference (tests/test_gpu_attention.py, test_gpu_attn_chunk_scores.py)
+attention call and its fp64 reference (tests/test_gpu_attention.py, test_gpu_attn_chunk_scores.py),
+the eager (softcap) score of csrc/common.h fast_score restated in torch with the marked cases of
+tests/test_gpu_attn_softcap.py (their teeth, too, asserted here from the references alone),
 and the order-revealing bf16 generator of the exact-order tests; tests/test_engine_cases_cpu.py
 pins what they draw. Last, the fp32 single-op kernels of the codec encoder and the Whisper decoder
 (tests/test_gpu_codec_enc_ops.py, test_gpu_whisper_ops.py): the module formulas that serve as
@@ -156,11 +158,12 @@ def decode_exact_attention(q, K, V, lens, scale, window=0):
 
 
 def decode_attention_call(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flash=False, window=0, cap=None,
-                          prepare=None, want_rc=0):
+                          prepare=None, want_rc=0, softcap=0.0):
     """One t5g_attention_decode(_flash) call on random bf16 q / K / V (attn_inputs, one query
     per row); returns the output (fp64, [B][Hq][D]) and the host inputs. cap: cache slots per
     (row, kv head), default L; prepare(q, K, V) edits the inputs in place before the upload;
-    want_rc != 0: the call must return that status and write nothing (returns None)."""
+    want_rc != 0: the call must return that status and write nothing (returns None); softcap:
+    None leaves the struct's field unset (the ctypes default), else it is passed through."""
     import ctypes as C
     from t5gemma_tts_amd import _lib
     lib = _lib.lib()
@@ -178,6 +181,8 @@ def decode_attention_call(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flas
     a = _lib.AttnDecodeArgs(B=B, n_heads=Hq, n_kv_heads=Hkv, head_dim=D, q=qd.data_ptr(), k_cache=Kd.data_ptr(),
                             v_cache=Vd.data_ptr(), cap=cap, kv_len=lens_d.data_ptr(), causal=causal, window=window,
                             scale=D ** -0.5, out=out.data_ptr(), work=work.data_ptr())
+    if softcap is not None:
+        a.softcap = softcap
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     fn = lib.t5g_attention_decode_flash if flash else lib.t5g_attention_decode
     if want_rc != 0:
@@ -192,6 +197,237 @@ def decode_attention_call(L, B, lens, Hq=8, Hkv=4, D=256, causal=1, seed=0, flas
         nt = B * Hkv
         assert int(work[-nt:].view(torch.int32).abs().sum().item()) == 0
     return got, q, K, V
+
+
+# ---------------------------------------------------------------------------
+# decode attention with the eager score (softcap > 0): tests/test_gpu_attn_softcap.py
+def _rbf(x):
+    """fp32 -> bf16 (round to nearest even) -> fp32."""
+    return x.float().to(BF16).float()
+
+
+def fast_score_ref(s_fp32, scale, softcap, drop=None):
+    """csrc/common.h fast_score restated: from the fp32 dot product, x scale; or, softcap > 0,
+    the five bf16 roundings of the eager score -- 0 bf16(q.k), 1 bf16(x scale), 2 bf16(/ softcap),
+    3 bf16(tanh), 4 bf16(x softcap) -- every operation in fp32 (the tanh correctly rounded to
+    fp32). drop: the rounding point left out (a reference-only tooth). Returns fp32."""
+    s = s_fp32.float()
+    sc = torch.tensor(scale, dtype=torch.float32)
+    if not softcap > 0:
+        return s * sc
+    cap = torch.tensor(softcap, dtype=torch.float32)
+
+    def r(i, x):
+        return x if drop == i else _rbf(x)
+
+    v = r(1, r(0, s) * sc)
+    w = r(2, v / cap)
+    return r(4, r(3, torch.tanh(w.double()).float()) * cap)
+
+
+def bf16_tie_margin(v):
+    """How far the fp64 values v lie from the nearest bf16 rounding tie, in bf16 steps (0 .. 0.5;
+    0.5: on a bf16 value). As trig_safe measures it."""
+    a = v.double().abs().clamp(min=2.0 ** -100)
+    e = torch.floor(torch.log2(a))
+    frac = torch.remainder(a / torch.exp2(e - 7), 1.0)
+    return (frac - 0.5).abs()
+
+
+def fast_score_margin(s_fp64, scale, softcap):
+    """The smallest bf16_tie_margin over fast_score's five rounding points, each value computed
+    in fp64 from the rounded value before it (the first from the fp64 dot product)."""
+    sc = float(torch.tensor(scale, dtype=torch.float32))
+    m = bf16_tie_margin(s_fp64)
+    a = _rbf(s_fp64.double()).double() * sc
+    m = torch.minimum(m, bf16_tie_margin(a))
+    b = _rbf(a).double() / softcap
+    m = torch.minimum(m, bf16_tie_margin(b))
+    c = torch.tanh(_rbf(b).double())
+    m = torch.minimum(m, bf16_tie_margin(c))
+    d = _rbf(c).double() * softcap
+    return torch.minimum(m, bf16_tie_margin(d))
+
+
+SCORE_VARIANTS = ("restated", "exact", "nocap", "late_scale")
+
+
+def decode_softcap_attention(q, K, V, lens, scale, softcap, window=0, variant="restated", drop=None):
+    """fp64 softmax and P.V of each row's query over its keys [lo, lens[b]) (decode_exact_attention's
+    range), on the scores of one variant of the softcap: "restated" the fp32 dot product through
+    fast_score_ref (what the kernels are to compute), "exact" fp64 softcap * tanh(s * scale /
+    softcap), and the two reference-only teeth "nocap" (s * scale: the softcap dropped) and
+    "late_scale" (tanh(s / softcap) * softcap * scale: the softcap before the scale)."""
+    assert variant in SCORE_VARIANTS and softcap > 0
+    B, Hq, D = q.shape
+    G = Hq // K.shape[1]
+    out = torch.zeros(B, Hq, D, dtype=torch.float64)
+    for b in range(B):
+        L = int(lens[b])
+        lo = max(0, L - window) if window > 0 else 0
+        for h in range(Hq):
+            s = K[b, h // G, lo:L].double() @ q[b, h].double()
+            if variant == "restated":
+                s = fast_score_ref(s.float(), scale, softcap, drop).double()   # drop: see fast_score_ref
+            elif variant == "exact":
+                s = softcap * torch.tanh(s * scale / softcap)
+            elif variant == "nocap":
+                s = s * scale
+            else:
+                s = torch.tanh(s / softcap) * softcap * scale
+            out[b, h] = torch.softmax(s, 0) @ V[b, h // G, lo:L].double()
+    return out
+
+
+# The cases. Plain randn inputs give scores near +-1, where the softcap is almost the identity,
+# so every row with two or more keys in range carries two markers per kv head h, along the
+# query q^ of the group's first head (q head h * G): the first key in range is
+# K = 50 q^ / (scale |q^|^2) with V = +4, the last K = 53 q^ / (scale |q^|^2) with V = -4 --
+# scaled scores of 50 and 53, about 38.1 and 39.3 after the softcap, so the marked heads' outputs
+# (about -2.2) hang on that gap. Every seed below has safe markers and teeth that hold
+# (softcap_case asserts both; tests/test_kernel_cases_cpu.py runs it): should an edit here make
+# one fail, another seed is the remedy, never a looser margin or bound.
+SOFTCAP = 50.0
+SOFTCAP_MARKS = (50.0, 53.0)
+SOFTCAP_SAFE = 2.0 ** -10   # of a bf16 step, at every rounding point of a marker's score
+
+
+def _sc(L, lens, seed, **kw):
+    return dict(dict(L=L, lens=lens, seed=seed, window=0, causal=1, cap=L, Hq=8, Hkv=4, D=256, nan_past=False,
+                     forms=(False, True), marks=None), **kw)
+
+
+# The markers at 50 and 53 take one path through the five roundings (800 -> 50 -> 1 -> 0.7617 -> 38,
+# 848 -> 53 -> 1.0625 -> 0.7852 -> 39.25), on which only a missing last rounding changes a
+# bit: the spread cases give every (row, kv head) its own first marker score
+# (marks[row * Hkv + head], the second 3 above it), chosen on the CPU so that the restated
+# reference with any one rounding left out moves some marked head by ten times the bound.
+# At head_dim 256 the scale is a power of two and roundings 0 and 1 are one rounding (leaving
+# one of them out changes no bit); head_dim 128 tells them apart.
+SPREAD_256 = (26.125, 27.125, 28.5, 30.125, 34.5, 38.0, 38.75, 39.5, 40.25, 41.25, 42.75, 43.5, 48.0, 49.5, 51.25, 53.25)
+SPREAD_128 = (26.0, 27.125, 28.5, 30.125, 31.125, 32.5, 34.5, 38.0, 38.75, 39.5, 42.75, 43.5, 63.75, 65.0, 67.5, 36.0)
+SPREAD_GAP = 1.5
+
+
+SOFTCAP_CASES = {
+    # chunk edges: rows of 2 and 64 keys (one chunk), 65 (a second chunk of one key) and L
+    "edges65": _sc(65, [65, 65, 64, 2], 6500),
+    "edges128": _sc(128, [128, 65, 64, 2], 12800),
+    "edges191": _sc(191, [191, 65, 64, 2], 19100),
+    # a 100-key window: chunks that start at key t - 99
+    "window100": _sc(300, [300, 251, 101, 64], 30000, window=100),
+    # the cross-attention shape: the per-op launch that stage A of the layer launch must equal
+    "cross": _sc(64, [60, 64, 9, 2], 6000, causal=0),
+    # NaN in K and V in every slot past each row's length, 70 slots past the longest row
+    "nan_past": _sc(191, [191, 130, 65, 64], 700, cap=191 + 70, nan_past=True),
+    # every instantiated (head_dim, group), 2 kv heads: both fast_score sites of attn.hip
+    "geom64x2": _sc(70, [70, 64, 9, 1], 6420, Hq=4, Hkv=2, D=64),
+    "geom128x2": _sc(70, [70, 64, 9, 1], 12820, Hq=4, Hkv=2, D=128),
+    "geom256x1": _sc(70, [70, 64, 9, 1], 25610, Hq=2, Hkv=2, D=256),
+    "geom256x2": _sc(70, [70, 64, 9, 1], 25620, Hq=4, Hkv=2, D=256),
+    # 32 rows, flash form
+    "rows32": _sc(130, [(130, 129, 65, 64, 2, 127, 70, 1)[i % 8] for i in range(32)], 3200, forms=(True,)),
+    # a marker score of its own per (row, kv head): every rounding point of fast_score
+    "spread256": _sc(150, [150, 65, 64, 2], 15000, marks=SPREAD_256),
+    "spread128": _sc(150, [150, 65, 64, 2], 15001, D=128, marks=SPREAD_128),
+}
+SPREAD_DROPS = {"spread256": (2, 3), "spread128": (0, 1, 2, 3)}
+
+
+def softcap_key_range(c, b):
+    L = c["lens"][b]
+    return (max(0, L - c["window"]) if c["window"] > 0 else 0), L
+
+
+def softcap_marks(c, b, h):
+    """The scaled scores planted on the first and the last key in range of (row b, kv head h)."""
+    if c["marks"] is None:
+        return SOFTCAP_MARKS
+    base = c["marks"][b * c["Hkv"] + h]
+    return base, base + SPREAD_GAP
+
+
+def softcap_prepare(c):
+    """prepare(q, K, V) of decode_attention_call for case c: the markers, then the NaN slots."""
+    G = c["Hq"] // c["Hkv"]
+    scale = float(torch.tensor(c["D"] ** -0.5, dtype=torch.float32))
+
+    def prepare(q, K, V):
+        for b in range(len(c["lens"])):
+            lo, hi = softcap_key_range(c, b)
+            if hi - lo >= 2:
+                for h in range(c["Hkv"]):
+                    qh = q[b, h * G].float()
+                    s0, s1 = softcap_marks(c, b, h)
+                    for key, score, v in ((lo, s0, 4.0), (hi - 1, s1, -4.0)):
+                        K[b, h, key] = (score / scale * qh / qh.norm() ** 2).to(BF16)
+                        V[b, h, key] = v
+            if c["nan_past"]:
+                K[b, :, hi:] = float("nan")
+                V[b, :, hi:] = float("nan")
+    return prepare
+
+
+@functools.lru_cache(maxsize=None)
+def softcap_case(name):
+    """Inputs, the references of every score variant, the bound, and what the GPU test relies on,
+    asserted here from the references alone: every marker's score is safe (more than
+    SOFTCAP_SAFE of a bf16 step from a tie at each of fast_score's five rounding points, so the
+    kernel's fp32 sum order cannot flip it), and "nocap" and "late_scale" each move every marked
+    head of every marked row by at least ten times the (aten-order, the wider) bound; a rounding
+    point left out moves them as the comment below says (50 / 53 cases: the last one; spread
+    cases, which have no "nocap" / "late_scale" teeth: SPREAD_DROPS).
+    Returns dict(c, q, K, V, ref: {variant: fp64 [B][Hq][D]}, bound: {flash: bound}, marked:
+    [(row, q head)], move: {variant: smallest move over the marked heads; "drop<i>" of a spread
+    case: marked heads moved by 4 bounds}, margin: smallest marker margin)."""
+    c = SOFTCAP_CASES[name]
+    B, G, D = len(c["lens"]), c["Hq"] // c["Hkv"], c["D"]
+    scale = D ** -0.5
+    q, K, V = attn_inputs(c["seed"], B, c["Hq"], c["Hkv"], D, B, c["cap"])
+    softcap_prepare(c)(q, K, V)
+    ref = {v: decode_softcap_attention(q, K, V, c["lens"], scale, SOFTCAP, c["window"], v) for v in SCORE_VARIANTS}
+    assert bool(torch.isfinite(ref["restated"]).all()), name
+    top = max(1.0, ref["restated"].abs().max().item())
+    bound = {False: 2.0 ** -6 * top, True: 2.0 ** -7 * top}
+    marked, margin = [], 0.5
+    for b in range(B):
+        lo, hi = softcap_key_range(c, b)
+        if hi - lo < 2:
+            continue
+        for h in range(c["Hkv"]):
+            marked.append((b, h * G))
+            s = K[b, h, [lo, hi - 1]].double() @ q[b, h * G].double()
+            margin = min(margin, fast_score_margin(s, scale, SOFTCAP).min().item())
+            # the restated scores of the two markers: about 38 and 39.3 (spread cases: 22 to 46,
+            # ordinary keys' e^-16 below), the last one the larger
+            r = fast_score_ref(s.float(), scale, SOFTCAP)
+            lim = (37.0, 40.0) if c["marks"] is None else (22.0, 46.0)
+            assert lim[0] <= r[0].item() < r[1].item() <= lim[1], (name, b, h, r.tolist())
+    assert len(marked) >= c["Hkv"] * (B - 1) // 2 and margin > SOFTCAP_SAFE, (name, c["seed"], margin)
+    move = {}
+    for v in ("nocap", "late_scale", "exact"):
+        d = (ref[v] - ref["restated"]).abs().amax(-1)
+        move[v] = min(d[b, h].item() for b, h in marked)
+    for v in ("nocap", "late_scale"):
+        # (a spread case's lower marker scores sit where the softcap is nearly linear: its teeth
+        # are the rounding points, below)
+        assert c["marks"] is not None or move[v] >= 10 * bound[False], (name, c["seed"], v, move[v], bound[False])
+    # the restated reference with rounding point i left out. A kernel that left it out would sit
+    # within its own error (at most the bound, were it otherwise right) of that reference, so a
+    # move of 4 bounds leaves 3 to fail by. Spread cases: rounding i moves that far on at least
+    # one marked head (a flipped marker moves its score by a whole bf16 step, 0.125 or 0.25).
+    # The 50 / 53 cases: only the last rounding shows on their markers, as a part of a step
+    # (38.086 -> 38, 39.258 -> 39.25): 0.108 on every marked head, 1.5 aten-order bounds or more.
+    for i in SPREAD_DROPS.get(name, (4,)):
+        d = (decode_softcap_attention(q, K, V, c["lens"], scale, SOFTCAP, c["window"], "restated", drop=i)
+             - ref["restated"]).abs().amax(-1)
+        if c["marks"] is None:
+            move["drop%d" % i] = min(d[b, h].item() for b, h in marked)
+            assert move["drop%d" % i] >= 1.5 * bound[False], (name, c["seed"], i, move["drop%d" % i], bound[False])
+        else:
+            move["drop%d" % i] = sum(d[b, h].item() >= 4 * bound[False] for b, h in marked)   # heads moved
+            assert move["drop%d" % i] >= 1, (name, c["seed"], i)
+    return dict(c=c, q=q, K=K, V=V, ref=ref, bound=bound, marked=marked, move=move, margin=margin)
 
 
 # window edges. A marked query is (row, t, marker key, alt): the marker -- 8 q / |q| for head 0

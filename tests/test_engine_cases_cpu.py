@@ -6,6 +6,7 @@ drew something else would leave a GPU test passing on cases it was not written f
 Each hash was recorded at the commit before the merge, with _utt_hash / _bits_hash below applied to
 the call named next to it (cfg as _cfg() makes it); the three copies of the default generator and
 the two of _hdr and of _run's draw gave equal hashes there."""
+import dataclasses
 import hashlib
 import json
 import os
@@ -100,8 +101,28 @@ def test_mid_config_is_made_once(monkeypatch):
         assert sd2 is sd and cfg2 is cfg and wsd is sd and len(calls) == 1
         assert wcfg.backbone.sliding_window == 100 != cfg.backbone.sliding_window
         assert calls[0] == json.load(open(os.path.join(GOLDEN, "golden_mid.json")))["weight_seed"]
+        # attn_implementation likewise: the config only, alone and together with a window
+        ecfg, esd = ec.mid_config(attn_implementation="eager")
+        bcfg, bsd = ec.mid_config(window=100, attn_implementation="eager")
+        assert esd is sd and bsd is sd and len(calls) == 1
+        assert cfg.backbone.attn_implementation == "sdpa" and cfg.backbone.softcap == 0.0
+        assert ecfg.backbone.attn_implementation == "eager" and ecfg.backbone.softcap == 50.0
+        assert ecfg.backbone.sliding_window == cfg.backbone.sliding_window
+        assert bcfg.backbone.softcap == 50.0 and bcfg.backbone.sliding_window == 100
+        assert ecfg == dataclasses.replace(cfg, backbone=dataclasses.replace(cfg.backbone, attn_implementation="eager"))
     finally:
         ec._mid_config.cache_clear()   # drop the stub's result
+
+
+def test_mid_weights_do_not_depend_on_attn_implementation():
+    """mid_config hands the eager engine the state dict it drew for the config's own sdpa: the
+    weights drawn for the eager config are the same (the digest golden_mid.json records)."""
+    from t5gemma_tts_amd.weights import state_dict_digest, synthetic_weights
+    meta = json.load(open(os.path.join(GOLDEN, "golden_mid.json")))
+    cfg = _cfg()
+    ecfg = dataclasses.replace(cfg, backbone=dataclasses.replace(cfg.backbone, attn_implementation="eager"))
+    assert cfg.backbone.softcap == 0.0 and ecfg.backbone.softcap == 50.0
+    assert state_dict_digest(synthetic_weights(ecfg, meta["weight_seed"])) == meta["weight_sha256"]
 
 
 def test_header_symbols_are_the_bound_signatures():

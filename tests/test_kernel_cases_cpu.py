@@ -1,7 +1,9 @@
 """What the kernel-level GPU tests of the fast path's encoder / prefill kernels take for granted
 before they launch anything, checked with no GPU (tests/kernel_cases.py): the teeth of the
 window and block cases come from the fp64 reference alone, the slab values tell a slab order,
-and the RoPE safe-set rule leaves the share of unsafe pairs it predicts."""
+the RoPE safe-set rule leaves the share of unsafe pairs it predicts, and the softcap cases of the
+decode attention (tests/test_gpu_attn_softcap.py) have safe markers and references that move
+when the softcap is dropped, misplaced or loses a rounding point."""
 import pytest
 import torch
 
@@ -36,6 +38,54 @@ def test_lost_block_rescale_moves_the_reference(window):
         assert (lo + 512) // 512 != 1
     else:
         assert (lo + 512) // 512 == 1
+
+
+@pytest.mark.parametrize("name", sorted(kc.SOFTCAP_CASES))
+def test_softcap_cases_have_teeth(name):
+    """tests/test_gpu_attn_softcap.py's cases, from the references alone (softcap_case asserts
+    them for the seed the GPU test uses): every marker's score lies more than 2^-10 of a bf16
+    step from a tie at each of fast_score's five rounding points; the 50 / 53 cases move every
+    marked head by ten times the aten-order bound when the softcap is dropped or applied after
+    the scale, and by 1.5 bounds when the last rounding is; the spread cases move some marked
+    head by 4 bounds for each rounding point their head_dim can tell."""
+    r = kc.softcap_case(name)
+    c, ref = r["c"], r["ref"]["restated"]
+    print(f"{name}: seed {c['seed']}, {len(r['marked'])} marked heads, smallest marker margin {r['margin']:.3g} "
+          f"of a step, bound {r['bound'][False]:.3g}, moves {r['move']}")
+    assert r["bound"][False] == 2.0 ** -6 * max(1.0, ref.abs().max().item()) == 2 * r["bound"][True]
+    assert r["margin"] > 2.0 ** -10
+    rows = {b for b, _ in r["marked"]}
+    assert rows == {b for b in range(len(c["lens"])) if min(c["lens"][b], c["window"] or c["lens"][b]) >= 2}
+    if c["marks"] is None:
+        assert r["move"]["nocap"] >= 10 * r["bound"][False] and r["move"]["late_scale"] >= 10 * r["bound"][False]
+        assert r["move"]["drop4"] >= 1.5 * r["bound"][False]
+        # the restatement, not the fp64 formula, is the reference: every marked head differs by
+        # more than the flash bound
+        assert r["move"]["exact"] > r["bound"][True]
+    else:
+        assert all(r["move"]["drop%d" % i] >= 1 for i in kc.SPREAD_DROPS[name])
+
+
+def test_fast_score_ref_rounding_points():
+    """The restatement on hand-computed values: 800 x 1/16 -> 50 -> 1 -> tanh 0.76159 -> 0.76171875
+    -> 38.0859 -> 38; 848 -> 53 -> 1.06 -> 1.0625 -> 0.78661 -> 0.78515625 -> 39.2578 -> 39.25;
+    softcap 0 is the plain fp32 product; at a power-of-two scale roundings 0 and 1 are one."""
+    s = torch.tensor([800.0, 848.0, 801.3, 16.7])
+    got = kc.fast_score_ref(s, 1 / 16, 50.0)
+    assert got[:3].tolist() == [38.0, 39.25, 38.0]
+    assert kc.fast_score_ref(s, 1 / 16, 0.0).tolist() == (s * (1 / 16)).tolist()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(4096, generator=g) * 400
+    full = kc.fast_score_ref(x, 1 / 16, 50.0)
+    assert torch.equal(full, kc.fast_score_ref(x, 1 / 16, 50.0, drop=0))
+    assert torch.equal(full, kc.fast_score_ref(x, 1 / 16, 50.0, drop=1))
+    for i in (2, 3, 4):
+        assert not torch.equal(full, kc.fast_score_ref(x, 1 / 16, 50.0, drop=i)), i
+    # every result is a bf16 value, odd, and below the cap
+    assert torch.equal(full, full.to(kc.BF16).float()) and torch.equal(full, -kc.fast_score_ref(-x, 1 / 16, 50.0))
+    assert full.abs().max().item() <= 50.0
+    # a value on a bf16 value is 0.5 from a tie, one on a tie 0
+    assert kc.bf16_tie_margin(torch.tensor([1.0, 1.00390625, 800.0, 802.0], dtype=torch.float64)).tolist() == [0.5, 0.0, 0.5, 0.0]
 
 
 @pytest.mark.parametrize("nsplit", [3, 5, 8])

@@ -27,7 +27,10 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.SamplerRow) == 48
     assert C.sizeof(_lib.SamplerState) == 48
     assert C.sizeof(_lib.LayerWeights) == 13 * 8
-    assert C.sizeof(_lib.AttnDecodeArgs) == 4 * 4 + 3 * 8 + 8 + 8 + 4 * 4 + 2 * 8
+    assert C.sizeof(_lib.AttnDecodeArgs) == 4 * 4 + 3 * 8 + 8 + 8 + 4 * 4 + 2 * 8 + 8
+    # softcap is appended: every earlier field keeps its offset
+    assert _lib.AttnDecodeArgs.softcap.offset == 88 and _lib.AttnDecodeArgs.work.offset == 80
+    assert _lib.AttnDecodeArgs().softcap == 0.0
     assert C.sizeof(_lib.GemvArgs) == 152
     # the three kernel-test hooks (csrc/engine_hooks.hip static_asserts the same sizes)
     assert C.sizeof(_lib.AttnPackedArgs) == 4 * 4 + 6 * 8 + 6 * 4 + 8
@@ -148,6 +151,27 @@ def test_attention_decode_reports_unbuilt_geometry(D, G):
                             kv_len=16, causal=1, window=0, scale=D ** -0.5, out=16, work=16)
     assert L.t5g_attention_decode(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
     assert L.t5g_attention_decode_flash(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+    # a softcap that is negative or not finite is a bad argument whatever the geometry; 50 is not
+    for bad in (-1.0, -50.0, float("nan"), float("inf"), float("-inf")):
+        a.softcap = bad
+        assert L.t5g_attention_decode(C.byref(a), None) == _lib.T5G_EINVAL, bad
+        assert L.t5g_attention_decode_flash(C.byref(a), None) == _lib.T5G_EINVAL, bad
+    a.softcap = 50.0
+    assert L.t5g_attention_decode(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+    assert L.t5g_attention_decode_flash(C.byref(a), None) == _lib.T5G_EUNSUPPORTED
+
+
+@pytest.mark.parametrize("flash", [False, True], ids=["aten_order", "flash"])
+def test_attention_decode_rejects_bad_softcap(flash):
+    """A built geometry (8 q / 4 kv heads x 256) with a negative or non-finite softcap:
+    T5G_EINVAL on the host, before any launch (the pointers are never dereferenced)."""
+    from t5gemma_tts_amd import _lib
+    L = _lib.lib()
+    fn = L.t5g_attention_decode_flash if flash else L.t5g_attention_decode
+    for bad in (-1.0, -1e-30, float("nan"), float("inf")):
+        a = _lib.AttnDecodeArgs(B=4, n_heads=8, n_kv_heads=4, head_dim=256, q=16, k_cache=16, v_cache=16, cap=200,
+                                kv_len=16, causal=1, window=0, scale=1 / 16, out=16, work=16, softcap=bad)
+        assert fn(C.byref(a), None) == _lib.T5G_EINVAL, bad
 
 
 def _packed_args(**kw):
